@@ -16,7 +16,12 @@ total work is fixed).  Random-init SD-2.1 weights (no network for checkpoints), 
 exit, nothing on stdout) when WORLD_SIZE != --gpus or fewer than --gpus devices are visible; ``n_gpus`` in the line is
 the process group's size and ``rccl_ranks`` an all-reduced counter (tests/test_bench_launch.py, gloo, stubbed step).
 
-Rank 0 prints ONE JSON line.  Extra objects on that line:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints the headline
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``) with the configuration and a finiteness
+check of the parameters.  ``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (float32 /
+float64, seeded inputs: two builds can be compared output for output).  ``--full`` adds everything else: per-kernel HIP
+events inside the timed region, an eager pass for the graphed convolutions, torch host synchronisations of one extra step,
+clock / power telemetry, the timed gradient all-reduce (N > 1), pair counts, and these objects on the line:
   roofline      the DOMINANT kernel of the step = the hand-written bf16 MFMA conv3x3 kernel (largest share
                 of GPU time): algorithmic FLOPs (2*N*H*W*Cout*9*Cin per launch) / its summed launch
                 duration, from HIP events recorded around every launch inside the timed region; peak =
@@ -208,7 +213,51 @@ def parse():
     ap.add_argument("--vsd", action="store_true",
                     help="BASELINE configs[4] diagnostic: NeTF VSD iteration (VAE + 2 frozen UNet + LoRA UNet fwd, "
                          "LoRA UNet fwd+bwd) on a synthetic 512^2 render, one view per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timing, rooflines, host-sync count, telemetry, pair counts and the "
+                         "CPU baseline (see the module docstring); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
+
+
+DUMP_MAX_ELEMENTS = 4 << 20          # per array; the whole dump stays under 64 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: one .npy per array, float64 kept, every other dtype as float32 (integer counts are exact there).
+    An array above DUMP_MAX_ELEMENTS is written as a fixed sample: the elements at sorted indices drawn with seed 0, so
+    two runs (or two builds) sample the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMENTS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"bench.py --dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB at '{name}'")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def sds_step_outputs(out: dict, gaussians) -> dict:
+    """What a caller of the SDS step receives: its returned scalars and the Gaussians it updated (parameters, their
+    gradients of this step, the view-summed view-space gradient)."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    for name, p in gaussians.named_parameters():
+        if p.numel() == 0:
+            continue
+        arrays["param_" + name.lstrip("_")] = p
+        if p.grad is not None:
+            arrays["grad_" + name.lstrip("_")] = p.grad
+    vs = getattr(gaussians, "viewspace_grad", None)
+    if vs is not None:
+        arrays["viewspace_grad"] = vs
+    return arrays
 
 
 def observed_host_syncs(step_fn) -> dict:
@@ -374,21 +423,27 @@ def vsd_main(args):
                     bucket = gdist.GradBucket(grads)
                 bucket.all_reduce_mean_(grads)
             opt.step()
+        return loss, lu
 
     for _ in range(args.warmup):
         step()
-    tele = Telemetry(device.index)
+    tele = Telemetry(device.index) if args.full else None
     gdist.barrier()
     torch.cuda.synchronize()
-    tele.start()
+    if tele is not None:
+        tele.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss, lu = step()
     torch.cuda.synchronize()
     gdist.barrier()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    telemetry = tele.stop()
+    telemetry = tele.stop() if tele is not None else None
+    if args.dump_outputs and rk == 0:
+        with torch.no_grad():
+            dump_outputs(args.dump_outputs, {"loss": loss, "lora_loss": lu, "image_grad": img.grad,
+                                             "lora_trainables": torch.cat([p.reshape(-1).float() for p in train])})
     # health (untimed): a replayed graph that went wrong shows up as non-finite adapters / image gradient
     with torch.no_grad():
         health = {"lora_params_finite": all(bool(torch.isfinite(p).all()) for p in train),
@@ -396,29 +451,33 @@ def vsd_main(args):
                   "image_grad_nonzero": bool(img.grad is not None and float(img.grad.abs().sum()) > 0)}
     if not all(health.values()):
         raise SystemExit(f"bench.py --vsd: unhealthy run {health}")
-    host_syncs = observed_host_syncs(step)
+    if args.full:
+        host_syncs = observed_host_syncs(step)
     if rk == 0:
-        tfl = 3 * UNET_TFLOP_PER_SAMPLE + 2 * VAE_TFLOP_PER_IMAGE + 3 * UNET_TFLOP_PER_SAMPLE
-        emit({"metric": "NeTF VSD iters/sec (VAE + 3 UNet fwd + LoRA-UNet fwd/bwd), 512^2, 1 view/GPU",
-                          "value": ws * args.steps / el, "unit": "view-iters/s", "n_gpus": ws, "steps": args.steps,
-                          "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
-                          "scaling": "weak", "vs_baseline": None,
-                          "dtype": "bf16" if not args.fp8 else "bf16 + fp8(e4m3) 3x3 convolutions of the three no-grad UNet forwards",
-                          "data": "synthetic",
-                          "config": {"workload": f"VSD step, SD-2.1 UNet + LoRA UNet (rank 4) random-init, batch 1, {res}^2 image leaf"
-                                                 + (" reduced to 512^2 for the VAE" if res != 512 else ""),
-                                     "hip_graphs": bool(gd.use_hip_graphs), "fp8_unet": bool(gd.fp8_unet),
-                                     "streams": ("three (caller: VAE + frozen UNet; LoRA no-grad forward; LoRA training pass + optimizer "
-                                                 "step inside guidance.lora_stream())" if _LORA_STREAM else
-                                                 "three inside the guidance, the reference's unedited call sequence"),
-                                     "torch_host_syncs_per_step_observed": host_syncs["count"],
-                                     "torch_host_sync_sites": host_syncs["sites"],
-                                     "fp8_sites_run": sum(getattr(n, "fp8").sites_run for n in (gd.unet, lora)
-                                                          if getattr(n, "fp8", None) is not None)},
-                          "health": health, "telemetry": telemetry,
-                          "roofline_dense": {"bound": "mfma", "achieved": tfl / (el / args.steps),
-                                             "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                                             "frac": tfl / (el / args.steps) / PEAK_BF16_TFLOPS}})
+        line = {"metric": "NeTF VSD iters/sec (VAE + 3 UNet fwd + LoRA-UNet fwd/bwd), 512^2, 1 view/GPU",
+                "value": ws * args.steps / el, "unit": "view-iters/s", "n_gpus": ws, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None,
+                "dtype": "bf16" if not args.fp8 else "bf16 + fp8(e4m3) 3x3 convolutions of the three no-grad UNet forwards",
+                "data": "synthetic",
+                "config": {"workload": f"VSD step, SD-2.1 UNet + LoRA UNet (rank 4) random-init, batch 1, {res}^2 image leaf"
+                                       + (" reduced to 512^2 for the VAE" if res != 512 else ""),
+                           "hip_graphs": bool(gd.use_hip_graphs), "fp8_unet": bool(gd.fp8_unet),
+                           "streams": ("three (caller: VAE + frozen UNet; LoRA no-grad forward; LoRA training pass + optimizer "
+                                       "step inside guidance.lora_stream())" if _LORA_STREAM else
+                                       "three inside the guidance, the reference's unedited call sequence"),
+                           "fp8_sites_run": sum(getattr(n, "fp8").sites_run for n in (gd.unet, lora)
+                                                if getattr(n, "fp8", None) is not None)},
+                "health": health}
+        if args.full:
+            tfl = 3 * UNET_TFLOP_PER_SAMPLE + 2 * VAE_TFLOP_PER_IMAGE + 3 * UNET_TFLOP_PER_SAMPLE
+            line["config"]["torch_host_syncs_per_step_observed"] = host_syncs["count"]
+            line["config"]["torch_host_sync_sites"] = host_syncs["sites"]
+            line["telemetry"] = telemetry
+            line["roofline_dense"] = {"bound": "mfma", "achieved": tfl / (el / args.steps),
+                                      "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                                      "frac": tfl / (el / args.steps) / PEAK_BF16_TFLOPS}
+        emit(line)
     if gdist.is_dist():
         torch.distributed.destroy_process_group()
 
@@ -522,6 +581,8 @@ def stub_main(args):
 def main():
     args = parse()
     launch_ranks_if_needed(args)
+    # what the step draws from torch's global generators (VSD noise / timesteps, LoRA init) repeats from run to run
+    torch.manual_seed(int(os.environ.get("RANK", "0")))
     _claim_stdout()
     if args.nn_lib:
         from garmentdreamer_amd import nn_ops as _nn
@@ -600,37 +661,114 @@ def main():
             else:
                 loop.optimizer.zero_grad(set_to_none=True)
             loss.backward()
-            return
+            return {"loss": loss.detach()}
         noise = torch.randn(V, 4, 64, 64, device=device, generator=gen)
         vae_noise = torch.randn(V, 4, 64, 64, device=device, generator=gen)
         t = torch.randint(20, 981, (V,), device=device, generator=gen)
-        loop.step(batch, noise=noise, timesteps=t, vae_noise=vae_noise)
+        return loop.step(batch, noise=noise, timesteps=t, vae_noise=vae_noise)
 
     from garmentdreamer_amd import nn_ops
     nn_ops.library_fallbacks(reset=True)       # counted over warm-up (where the graphs are captured) AND the timed region
     for s in range(args.warmup):
         one_step(s)
     torch.cuda.synchronize()
-    _native.profile_reset()
-    _native.profile_enable(True)
-    if not args.raster_only:
-        nn_ops.conv_profile(enable=True, reset=True)
-    tele = Telemetry(device.index)
+    if args.full:
+        _native.profile_reset()
+        _native.profile_enable(True)
+        if not args.raster_only:
+            nn_ops.conv_profile(enable=True, reset=True)
+    tele = Telemetry(device.index) if args.full else None
     gdist.barrier()
     torch.cuda.synchronize()
-    tele.start()
-    loop.time_collectives = ws > 1 and not args.raster_only      # HIP events either side of the gradient all-reduce
+    if tele is not None:
+        tele.start()
+    loop.time_collectives = args.full and ws > 1 and not args.raster_only      # HIP events either side of the gradient all-reduce
+    out = {}
     t0 = time.perf_counter()
     for s in range(args.steps):
-        one_step(args.warmup + s)
+        out = one_step(args.warmup + s)
     torch.cuda.synchronize()
     gdist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    telemetry = tele.stop()
+    telemetry = tele.stop() if tele is not None else None
+    if args.dump_outputs and rk == 0:
+        dump_outputs(args.dump_outputs, sds_step_outputs(out, gaussians))
+    fallbacks = nn_ops.library_fallbacks()
+    graphs_active = bool(guidance is not None and guidance.cfg.use_hip_graphs)   # False if capture failed / was refused
+    if ws > 1:
+        t = torch.tensor([elapsed], device=device, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    # ---- health (untimed): a fast step that has silently gone non-finite renders nothing and times "well" ----
+    with torch.no_grad():
+        params_finite = all(bool(torch.isfinite(p).all()) for p in gaussians.parameters())
+    if not params_finite:
+        raise SystemExit("bench.py: Gaussian parameters are not finite after the timed steps -- the measurement is void")
+
+    report = full_report(args, loop, guidance, one_step, device, view_ids, ws, elapsed, telemetry,
+                         graphs_active) if args.full else None
+
+    acct = rank_accounting(device, lr)
+    if acct["n_gpus"] != args.gpus or acct["rccl_ranks"] != args.gpus:
+        raise SystemExit(f"bench.py: rank accounting {acct} does not match --gpus {args.gpus}")
+    if rk == 0:
+        V = len(view_ids)
+        line = {
+            "metric": METRIC, "value": args.steps / elapsed, "unit": "iters/s", "n_gpus": acct["n_gpus"],
+            "rccl_ranks": acct["rccl_ranks"], "distinct_devices": acct["distinct_devices"],
+            "collective_backend": acct["backend"], "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None,
+            "dtype": "bf16" if not args.fp8 else "bf16 + fp8(e4m3) 3x3 convolutions of the no-grad UNet forward",
+            "data": "synthetic",
+            "config": {"workload": (f"SDS loop: {args.gaussians} Gaussians x {args.views} views @{args.res}^2, "
+                                    f"SD-2.1 UNet+VAE random-init, {V} view(s)/GPU"),
+                       "gaussians": args.gaussians, "views": args.views, "resolution": args.res,
+                       "views_per_gpu": V, "parallelism": f"view-sharded dp{ws}",
+                       "raster": "per-view loop" if args.per_view_raster else "batched",
+                       "raster_only": bool(args.raster_only), "hip_graphs": graphs_active,
+                       "fp8_unet_sites": (guidance.unet.fp8.sites_run if guidance is not None and
+                                          getattr(guidance.unet, "fp8", None) is not None else 0),
+                       "raster_binning": ("tile-bucketed (count / scan / scatter / per-tile LDS counting sort; radix fallback beyond 4096 "
+                                          "instances per tile)" if os.environ.get("GD_RASTER_BUCKETS", "1") != "0"
+                                          else "global radix sort (GD_RASTER_BUCKETS=0)"),
+                       "own_gemm_geglu": os.environ.get("GD_OWN_GEMM", "1") != "0",
+                       "batch_invariant": bool(loop.batch_invariant),
+                       "batch_invariant_route_scale": (loop._route_kr()[0] if loop.batch_invariant else 1),
+                       "raster_forward_host_syncs_in_timed_region": (
+                           0 if loop.capacity is not None and loop.capacity.calls_sync_free >= args.warmup + args.steps - 1
+                           else args.steps),
+                       "raster_instance_capacity": None if loop.capacity is None else loop.capacity.value,
+                       "library_fallbacks": sum(fallbacks.values()),
+                       "library_fallback_sites": fallbacks or None,
+                       "library_override": {"nn": args.nn_lib, "raster": args.raster_lib}
+                       if (args.nn_lib or args.raster_lib) else None},
+            "health": {"params_finite": params_finite},
+        }
+        if args.full:
+            line["config"].update(report.pop("config"))
+            line["health"].update(report.pop("health"))
+            line.update(report)
+            if ws == 1 and not args.no_cpu_baseline:
+                try:
+                    line["cpu_baseline"] = cpu_baseline(args)
+                except Exception as e:  # the baseline is reporting only; never fail the bench line on it
+                    line["cpu_baseline"] = {"value": None, "unit": "iters/s", "cores": 0, "kind": "port",
+                                            "sample": f"failed: {type(e).__name__}: {e}"}
+        emit(line)
+    if gdist.is_dist():
+        torch.distributed.destroy_process_group()
+
+
+def full_report(args, loop, guidance, one_step, device, view_ids, ws, elapsed, telemetry, graphs_active) -> dict:
+    """--full: what the line carries beyond the headline -- per-kernel times of the timed region (and of an eager pass for
+    the graphed convolutions), torch host synchronisations of one extra step, pair counts, rooflines, counter-file traffic,
+    the timed all-reduce.  Runs after the timed steps on every rank; returns the fields to merge into rank 0's line."""
+    from garmentdreamer_amd import _native, nn_ops
     coll_n, coll_ms, coll_bytes = loop.collective_times()
     loop.time_collectives = False
-    fallbacks = nn_ops.library_fallbacks()
     _native.profile_enable(False)
     prof = _native.profile_read()
     conv_ms, conv_n, conv_flops = nn_ops.conv_profile(enable=False) if not args.raster_only else (0.0, 0, 0.0)
@@ -638,7 +776,6 @@ def main():
     host_syncs = observed_host_syncs(lambda: one_step(args.warmup + args.steps + 1000))     # untimed, after the counters are read
     conv_steps = args.steps
     conv_note = "HIP events around every launch inside the timed region"
-    graphs_active = bool(guidance is not None and guidance.cfg.use_hip_graphs)   # False if capture failed / was refused
     if not args.raster_only and conv_n == 0:
         # The timed region replays the UNet / VAE as hipGraphs; launches inside a graph cannot be bracketed by
         # events, so the same kernels are timed in an eager pass of the same workload right after the timed region.
@@ -653,17 +790,6 @@ def main():
         guidance.cfg.use_hip_graphs = graphs_active
         conv_note = ("HIP events around every launch in an eager (non-graph) pass of the same workload run right after "
                      "the timed region, whose UNet/VAE launches are replayed from hipGraphs")
-    if ws > 1:
-        t = torch.tensor([elapsed], device=device, dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    # ---- health (untimed): a fast step that has silently gone non-finite renders nothing and times "well" ----
-    with torch.no_grad():
-        params_finite = all(bool(torch.isfinite(p).all()) for p in gaussians.parameters())
-    if not params_finite:
-        raise SystemExit("bench.py: Gaussian parameters are not finite after the timed steps -- the measurement is void")
-
     # ---- work accounting (untimed) ----
     counts = count_pairs(loop, camera_batch(args, args.warmup, view_ids), device)
     if counts["num_rendered"] <= 0:
@@ -784,74 +910,33 @@ def main():
             kernels_per_step = sum(float(r["CallsPerStep"]) for r in csv.DictReader(open(steady)))
         except Exception:
             pass
-    acct = rank_accounting(device, lr)
-    if acct["n_gpus"] != args.gpus or acct["rccl_ranks"] != args.gpus:
-        raise SystemExit(f"bench.py: rank accounting {acct} does not match --gpus {args.gpus}")
-    if rk == 0:
-        V = len(view_ids)
-        line = {
-            "metric": METRIC, "value": args.steps / elapsed, "unit": "iters/s", "n_gpus": acct["n_gpus"],
-            "rccl_ranks": acct["rccl_ranks"], "distinct_devices": acct["distinct_devices"],
-            "collective_backend": acct["backend"], "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None,
-            "dtype": "bf16" if not args.fp8 else "bf16 + fp8(e4m3) 3x3 convolutions of the no-grad UNet forward",
-            "data": "synthetic",
-            "config": {"workload": (f"SDS loop: {args.gaussians} Gaussians x {args.views} views @{args.res}^2, "
-                                    f"SD-2.1 UNet+VAE random-init, {V} view(s)/GPU"),
-                       "gaussians": args.gaussians, "views": args.views, "resolution": args.res,
-                       "views_per_gpu": V, "parallelism": f"view-sharded dp{ws}",
-                       "grad_allreduce": None if not coll_n else {
-                           "ms_per_step": coll_ms * coll_n / args.steps, "bytes": coll_bytes, "calls_per_step": coll_n / args.steps,
-                           "note": "HIP events on the step's stream either side of the ONE data-path collective (flat fp32 Gaussian "
-                                   "gradients incl. the view-space tail, in place, blocking after the backward pass); rank 0's view"},
-                       "raster": "per-view loop" if args.per_view_raster else "batched",
-                       "raster_only": bool(args.raster_only), "hip_graphs": graphs_active,
-                       "fp8_unet_sites": (guidance.unet.fp8.sites_run if guidance is not None and
-                                          getattr(guidance.unet, "fp8", None) is not None else 0),
-                       "kernels_per_step": kernels_per_step,
-                       "raster_binning": ("tile-bucketed (count / scan / scatter / per-tile LDS counting sort; radix fallback beyond 4096 "
-                                          "instances per tile)" if os.environ.get("GD_RASTER_BUCKETS", "1") != "0"
-                                          else "global radix sort (GD_RASTER_BUCKETS=0)"),
-                       "own_gemm_geglu": os.environ.get("GD_OWN_GEMM", "1") != "0",
-                       "batch_invariant": bool(loop.batch_invariant),
-                       "batch_invariant_route_scale": (loop._route_kr()[0] if loop.batch_invariant else 1),
-                       "raster_forward_host_syncs_in_timed_region": (
-                           0 if loop.capacity is not None and loop.capacity.calls_sync_free >= args.warmup + args.steps - 1
-                           else args.steps),
-                       "raster_instance_capacity": None if loop.capacity is None else loop.capacity.value,
-                       "torch_host_syncs_per_step_observed": host_syncs["count"], "torch_host_sync_sites": host_syncs["sites"],
-                       "library_fallbacks": sum(fallbacks.values()),
-                       "library_fallback_sites": fallbacks or None,
-                       "library_override": {"nn": args.nn_lib, "raster": args.raster_lib}
-                       if (args.nn_lib or args.raster_lib) else None},
-            "roofline": roofline_conv if roofline_conv is not None else roofline,
-            "roofline_raster_bwd": roofline,
-            "raster_kernels_ms_per_step": {k: v[0] / max(args.steps, 1) for k, v in prof.items()},
-            "pair_counts_rank0": counts,
-            "health": {"params_finite": params_finite, "visible_after_timed_steps": counts["visible"]},
-            "telemetry": telemetry,
-        }
-        for r in (line["roofline"], line["roofline_raster_bwd"]):
-            if r is not None:
-                r["clock_mhz_mean"], r["power_w_mean"] = telemetry.get("clock_mhz_mean"), telemetry.get("power_w_mean")
-        if not args.raster_only:
-            dense_tflop = V * (2 * UNET_TFLOP_PER_SAMPLE + 2 * VAE_TFLOP_PER_IMAGE)
-            raster_ms = sum(v[0] for v in prof.values()) / max(args.steps, 1)
-            dense_s = max(elapsed / args.steps - raster_ms * 1e-3, 1e-9)
-            line["roofline_dense"] = {"bound": "mfma", "achieved": dense_tflop / dense_s, "peak": PEAK_BF16_TFLOPS,
-                                      "unit": "TFLOP/s", "frac": dense_tflop / dense_s / PEAK_BF16_TFLOPS,
-                                      "tflop_per_step_per_gpu": dense_tflop,
-                                      "note": "step time minus rasterizer kernel time; includes Adam, losses, host gaps"}
-        if ws == 1 and not args.no_cpu_baseline:
-            try:
-                line["cpu_baseline"] = cpu_baseline(args)
-            except Exception as e:  # the baseline is reporting only; never fail the bench line on it
-                line["cpu_baseline"] = {"value": None, "unit": "iters/s", "cores": 0, "kind": "port",
-                                        "sample": f"failed: {type(e).__name__}: {e}"}
-        emit(line)
-    if gdist.is_dist():
-        torch.distributed.destroy_process_group()
+    V = len(view_ids)
+    report = {
+        "config": {"grad_allreduce": None if not coll_n else {
+                       "ms_per_step": coll_ms * coll_n / args.steps, "bytes": coll_bytes, "calls_per_step": coll_n / args.steps,
+                       "note": "HIP events on the step's stream either side of the ONE data-path collective (flat fp32 Gaussian "
+                               "gradients incl. the view-space tail, in place, blocking after the backward pass); rank 0's view"},
+                   "kernels_per_step": kernels_per_step,
+                   "torch_host_syncs_per_step_observed": host_syncs["count"], "torch_host_sync_sites": host_syncs["sites"]},
+        "roofline": roofline_conv if roofline_conv is not None else roofline,
+        "roofline_raster_bwd": roofline,
+        "raster_kernels_ms_per_step": {k: v[0] / max(args.steps, 1) for k, v in prof.items()},
+        "pair_counts_rank0": counts,
+        "health": {"visible_after_timed_steps": counts["visible"]},
+        "telemetry": telemetry,
+    }
+    for r in (report["roofline"], report["roofline_raster_bwd"]):
+        if r is not None:
+            r["clock_mhz_mean"], r["power_w_mean"] = telemetry.get("clock_mhz_mean"), telemetry.get("power_w_mean")
+    if not args.raster_only:
+        dense_tflop = V * (2 * UNET_TFLOP_PER_SAMPLE + 2 * VAE_TFLOP_PER_IMAGE)
+        raster_ms = sum(v[0] for v in prof.values()) / max(args.steps, 1)
+        dense_s = max(elapsed / args.steps - raster_ms * 1e-3, 1e-9)
+        report["roofline_dense"] = {"bound": "mfma", "achieved": dense_tflop / dense_s, "peak": PEAK_BF16_TFLOPS,
+                                    "unit": "TFLOP/s", "frac": dense_tflop / dense_s / PEAK_BF16_TFLOPS,
+                                    "tflop_per_step_per_gpu": dense_tflop,
+                                    "note": "step time minus rasterizer kernel time; includes Adam, losses, host gaps"}
+    return report
 
 
 def _cams_on(cb, device):

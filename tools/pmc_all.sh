@@ -14,7 +14,7 @@ groups=("FETCH_SIZE GRBM_GUI_ACTIVE" "WRITE_SIZE GRBM_GUI_ACTIVE" \
 i=0
 for g in "${groups[@]}"; do
   rm -rf /tmp/pmca_$i
-  rocprofv3 --kernel-trace --pmc $g --output-format csv -d /tmp/pmca_$i -o pmc -- python bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline --no-graphs > /tmp/pmca_$i.log 2>&1
+  rocprofv3 --kernel-trace --pmc $g --output-format csv -d /tmp/pmca_$i -o pmc -- python bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline --no-graphs > /tmp/pmca_$i.log 2>&1
   echo "pass $i ($g): rc $?" >&2
   i=$((i+1))
 done
@@ -86,7 +86,7 @@ for k, e in res.items():
         e["valu_insts_per_launch"] = e["SQ_INSTS_VALU"]
 meta = {"kernel_source_hash": bench.kernel_source_hash(),
         "workload": {"gaussians": _w.gaussians, "views": _w.views, "res": _w.res},
-        "method": ("rocprofv3 --kernel-trace --pmc <group> in separate passes of `python bench.py --steps 2 --warmup 1 "
+        "method": ("rocprofv3 --kernel-trace --pmc <group> in separate passes of `python bench.py --full --steps 2 --warmup 1 "
                    "--no-graphs`; values are averages per launch over the sampled launches; FETCH_SIZE x2 (gfx950), KiB; "
                    "mfma_util = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), hbm_gbps = hbm_bytes_per_launch / "
                    "avg_duration_us_profiled, clock_ghz = GRBM_GUI_ACTIVE / 8 / duration (all under the profiler)"),

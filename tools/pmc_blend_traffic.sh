@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for g in "FETCH_SIZE" "WRITE_SIZE"; do
-  rm -rf /tmp/pq; rocprofv3 --kernel-trace --pmc $g --output-format csv -d /tmp/pq -o p -- python bench.py --raster-only --no-cpu-baseline --steps 3 --warmup 1 > /dev/null 2>&1
+  rm -rf /tmp/pq; rocprofv3 --kernel-trace --pmc $g --output-format csv -d /tmp/pq -o p -- python bench.py --full --raster-only --no-cpu-baseline --steps 3 --warmup 1 > /dev/null 2>&1
   python - <<'PY'
 import csv, glob, collections
 agg = collections.defaultdict(float); cnt = collections.Counter()

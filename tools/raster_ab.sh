@@ -25,7 +25,7 @@ PY
   exit 0
 fi
 for so in "" ablate/libgd_raster_*.so; do
-  timeout 300 python bench.py ${so:+--raster-lib $PWD/$so} --raster-only --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full ${so:+--raster-lib $PWD/$so} --raster-only --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | tail -1 | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); r=d['raster_kernels_ms_per_step']; print('${so:-product}', ' '.join('%s %.4f' % (k, v) for k, v in r.items()), 'frac %.4f' % d['roofline_raster_bwd']['frac'])

@@ -2,7 +2,7 @@
 # rocprofv3 per-kernel stats of the raster-only benchmark (8 views x 512^2, 100k Gaussians)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/rstats
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rstats -o r -- python bench.py --raster-only --no-cpu-baseline --steps 20 --warmup 3 > /tmp/rstats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rstats -o r -- python bench.py --full --raster-only --no-cpu-baseline --steps 20 --warmup 3 > /tmp/rstats.log 2>&1
 f=$(find /tmp/rstats -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys

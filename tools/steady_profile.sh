@@ -3,7 +3,7 @@
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/prof_sp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_sp -o bench -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline "$@" > /tmp/prof_sp.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_sp -o bench -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline "$@" > /tmp/prof_sp.log 2>&1
 tr=$(find /tmp/prof_sp -name "*kernel_trace.csv" | head -1)
 python tools/steady_stats.py "$tr" $out --skip 2
 python - $out <<'PY'

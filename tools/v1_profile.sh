@@ -4,7 +4,7 @@ V=${VIEWS:-1}
 python bench.py --views $V --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | cut -c1-200
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/v1p
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/v1p -o v -- python bench.py --views $V --steps 20 --warmup 4 --no-cpu-baseline > /tmp/v1p.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/v1p -o v -- python bench.py --full --views $V --steps 20 --warmup 4 --no-cpu-baseline > /tmp/v1p.log 2>&1
 tail -1 /tmp/v1p.log | cut -c1-200
 tr=$(find /tmp/v1p -name "*kernel_trace.csv" | head -1)
 mkdir -p gpurun_out

@@ -3,7 +3,7 @@
 # largest first, with the kernels either side (rocprofv3 kernel trace)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/vsdg
-rocprofv3 --kernel-trace --output-format csv -d /tmp/vsdg -o v -- python bench.py ${BENCH_ARGS:---vsd} --steps 8 --warmup 4 > /tmp/vsdg.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/vsdg -o v -- python bench.py --full ${BENCH_ARGS:---vsd} --steps 8 --warmup 4 > /tmp/vsdg.log 2>&1
 tail -1 /tmp/vsdg.log | cut -c100-230
 tr=$(find /tmp/vsdg -name "*kernel_trace.csv" | head -1)
 python - "$tr" <<'PY'

@@ -2,7 +2,7 @@
 # per-kernel stats of the VSD iteration (bench.py --vsd), steady part
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/vsdp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/vsdp -o v -- python bench.py --vsd --steps 6 --warmup 3 > /tmp/vsdp.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/vsdp -o v -- python bench.py --full --vsd --steps 6 --warmup 3 > /tmp/vsdp.log 2>&1
 tail -1 /tmp/vsdp.log | cut -c1-300
 f=$(find /tmp/vsdp -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'

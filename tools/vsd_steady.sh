@@ -2,7 +2,7 @@
 # steady-state per-kernel stats of the VSD iteration (bench.py --vsd): rocprofv3 kernel trace, warm-up / capture steps cut off
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf /tmp/vsdp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/vsdp -o v -- python bench.py --vsd --steps 8 --warmup 4 > /tmp/vsdp.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/vsdp -o v -- python bench.py --full --vsd --steps 8 --warmup 4 > /tmp/vsdp.log 2>&1
 tail -1 /tmp/vsdp.log | cut -c100-200
 tr=$(find /tmp/vsdp -name "*kernel_trace.csv" | head -1)
 python - "$tr" ${1:-gpurun_out/vsd_steady.csv} <<'PY'
