@@ -11,6 +11,7 @@ NN_SOURCES = [
     ("nn_linear.hip", []),
     ("nn_lora.hip", []),
     ("nn_gemm.hip", []),
+    ("nn_vae_decoder.hip", []),
 ]
 
 

@@ -1,4 +1,4 @@
-"""Stable-Diffusion-2.1 UNet, VAE encoder and DDIM noise schedule, restated for PyTorch-ROCm.
+"""Stable-Diffusion-2.1 UNet, VAE (encoder; decoder for previews) and DDIM noise schedule, restated for PyTorch-ROCm.
 
 The reference obtains these from the un-vendored dependency ``diffusers==0.19.0``
 (Garment_3DGS/requirements.txt:12; call sites Garment_3DGS/threestudio/models/guidance/
@@ -878,7 +878,7 @@ class _QuantConv(nn.Conv2d):
 class AutoencoderKLEncoder(nn.Module):
     """Encoder half of AutoencoderKL: ``encode(x).latent_dist.sample()`` as the reference calls it
     (stable_diffusion_guidance.py:165-166).  The decoder is only used by ``guidance_eval`` previews
-    (disabled in the pipeline: GaussianDreamer.py:244) and is out of scope."""
+    (disabled in the pipeline: GaussianDreamer.py:244): AutoencoderKLDecoder / AutoencoderKL below."""
 
     config = _VAEConfig()
 
@@ -889,6 +889,102 @@ class AutoencoderKLEncoder(nn.Module):
 
     def encode(self, x):
         return _EncodeOutput(DiagonalGaussianDistribution(self.quant_conv(self.encoder(x.to(self.quant_conv.weight.dtype)))))
+
+
+class _VAEUpBlock(nn.Module):
+    """diffusers ``UpDecoderBlock2D``: ``layers_per_block + 1`` ResnetBlock2D (eps 1e-6), then nearest x2 + conv."""
+
+    def __init__(self, in_ch, out_ch, n_layers, up: bool):
+        super().__init__()
+        self.resnets = nn.ModuleList(
+            [ResnetBlock2D(in_ch if i == 0 else out_ch, out_ch, None, eps=1e-6) for i in range(n_layers)])
+        self.upsamplers = nn.ModuleList([Upsample2D(out_ch)]) if up else None
+
+    def forward(self, x):
+        for r in self.resnets:
+            x = r(x)
+        if self.upsamplers is not None:
+            x = self.upsamplers[0](x)
+        return x
+
+
+class Decoder(nn.Module):
+    """diffusers' VAE ``Decoder``: conv_in -> mid block -> up blocks (lowest resolution first) -> GroupNorm + SiLU -> conv_out.
+    The two ends run fused with their neighbours (AutoencoderKLDecoder.decode: nn_ops.vae_decode_stem / vae_decode_head);
+    ``body`` is everything between them, on the encoder's and UNet's blocks."""
+
+    def __init__(self, out_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4):
+        super().__init__()
+        ch = block_out_channels
+        self.conv_in = nn.Conv2d(latent_channels, ch[-1], 3, padding=1)
+        self.mid_block = _VAEMidBlock(ch[-1])
+        self.up_blocks = nn.ModuleList()
+        rev = list(reversed(ch))
+        out = rev[0]
+        for i, c in enumerate(rev):
+            inp, out = out, c
+            self.up_blocks.append(_VAEUpBlock(inp, out, layers_per_block + 1, up=i != len(ch) - 1))
+        self.conv_norm_out = nn.GroupNorm(32, ch[0], eps=1e-6)
+        self.conv_out = nn.Conv2d(ch[0], out_channels, 3, padding=1)
+
+    def body(self, x):
+        x = self.mid_block(x)
+        for b in self.up_blocks:
+            x = b(x)
+        return x
+
+    def forward(self, z):
+        return self.conv_out(F.silu(self.conv_norm_out(self.body(self.conv_in(z)))))
+
+
+class _DecodeOutput:
+    def __init__(self, sample):
+        self.sample = sample
+
+
+class _VAEDecoderMixin:
+    """``decode`` / ``decode_to_image`` of a module holding ``post_quant_conv`` and ``decoder``."""
+
+    def _decode(self, z, inv_scale: float, mode: str):
+        d, pq = self.decoder, self.post_quant_conv
+        x = nn_ops.vae_decode_stem(z, inv_scale, pq.weight, pq.bias, d.conv_in.weight, d.conv_in.bias)
+        x = d.body(x.contiguous(memory_format=torch.channels_last) if x.is_cuda else x)
+        n = d.conv_norm_out
+        return nn_ops.vae_decode_head(x, n.weight, n.bias, n.num_groups, n.eps, d.conv_out.weight, d.conv_out.bias, mode)
+
+    @torch.no_grad()
+    def decode(self, z):
+        """diffusers' ``AutoencoderKL.decode(z).sample``: ``z`` = latents / scaling_factor; the sample in [-1, 1] convention,
+        in the weights' dtype."""
+        return _DecodeOutput(self._decode(z, 1.0, "raw"))
+
+    @torch.no_grad()
+    def decode_to_image(self, latents):
+        """SCALED latents [N, 4, h, w] -> fp32 image [N, 3, 8h, 8w] in [0, 1] = ``clamp(decode(latents / scaling_factor)
+        * 0.5 + 0.5, 0, 1)``: the NCHW view of a contiguous NHWC buffer (``.permute(0, 2, 3, 1)`` is free)."""
+        return self._decode(latents, 1.0 / self.config.scaling_factor, "image")
+
+
+class AutoencoderKLDecoder(_VAEDecoderMixin, nn.Module):
+    """Decoder half of AutoencoderKL (``post_quant_conv`` + ``decoder``, diffusers' state-dict keys): loads from the same
+    SD-2.1 VAE safetensors file as AutoencoderKLEncoder."""
+
+    config = _VAEConfig()
+
+    def __init__(self, block_out_channels=(128, 256, 512, 512)):
+        super().__init__()
+        self.post_quant_conv = nn.Conv2d(4, 4, 1)
+        self.decoder = Decoder(block_out_channels=block_out_channels)
+
+
+class AutoencoderKL(_VAEDecoderMixin, AutoencoderKLEncoder):
+    """The whole VAE.  The decoder's parameters are registered after the encoder's, so ``init_random_`` with one seed gives
+    the encoder half AutoencoderKLEncoder would get."""
+
+    def __init__(self, block_out_channels=(128, 256, 512, 512)):
+        super().__init__(block_out_channels)
+        self.post_quant_conv = nn.Conv2d(4, 4, 1)
+        self.decoder = Decoder(block_out_channels=block_out_channels)
 
 
 # ----------------------------------------------------------------------------------------------

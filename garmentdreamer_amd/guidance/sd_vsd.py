@@ -97,6 +97,7 @@ class StableDiffusionVSD(nn.Module):
         if unet is None:
             with torch.device(self.device):
                 unet = sd21.init_random_(sd21.UNet2DConditionModel(), init_seed)
+        self._vae_self_built, self._own_decoder, self._init_seed = vae is None, (), init_seed
         if vae is None:
             with torch.device(self.device):
                 vae = sd21.init_random_(sd21.AutoencoderKLEncoder(), init_seed + 1)
@@ -281,6 +282,25 @@ class StableDiffusionVSD(nn.Module):
         if posterior is None:
             posterior = self.vae.encode(x).latent_dist
         return posterior.sample(vae_noise) * self.vae.config.scaling_factor
+
+    @torch.no_grad()
+    def decode_latents(self, latents):
+        """latents -> [B, 3, 8 h, 8 w] image in [0, 1] (sd_vsd_utils.py:266-272, no resize).  ``self.vae`` decodes if it can;
+        a VAE this object built itself gets a decoder half built on first use (``init_random_(..., init_seed + 2)``)."""
+        vae = self.vae
+        if not hasattr(vae, "decode"):
+            if not self._vae_self_built:
+                raise RuntimeError("decode_latents needs a VAE with a decoder (pass vae=<object with .decode>); the supplied "
+                                   "VAE has the encoder half only")
+            if not self._own_decoder:
+                from .stable_diffusion_guidance import _build_decoder
+                self._own_decoder = (_build_decoder(self.device, self.dtype, None, self._init_seed + 2),)
+            vae = self._own_decoder[0]
+        if isinstance(vae, sd21._VAEDecoderMixin):
+            return vae.decode_to_image(latents).to(latents.dtype)
+        latents = 1 / vae.config.scaling_factor * latents
+        imgs = vae.decode(latents).sample
+        return (imgs / 2 + 0.5).clamp(0, 1)
 
     def _fp8_calibrating(self, net) -> bool:
         """True while ``net`` (a UNet with an Fp8State) still has to run eager bf16 calibration forwards; counts one."""

@@ -98,6 +98,8 @@ class StableDiffusionGuidance(nn.Module):
                 sd21.load_diffusers_weights(unet, self.cfg.unet_weights)
             else:
                 sd21.init_random_(unet, self.cfg.init_seed)
+        self._vae_self_built = vae is None       # decode_latents may then build the decoder half itself (on first use)
+        self._own_decoder = ()
         if vae is None:
             with torch.device(self.device):
                 vae = sd21.AutoencoderKLEncoder()
@@ -385,16 +387,30 @@ class StableDiffusionGuidance(nn.Module):
             guidance_out.update({"eval": guidance_eval_out})
         return guidance_out
 
+    def _decoder_vae(self):
+        """The VAE that decodes: ``self.vae`` if it has ``decode``; else, when this guidance built its VAE itself, an
+        sd21.AutoencoderKLDecoder built on first use (about 99 MB in bf16: the SDS loop never needs it) from
+        ``cfg.vae_weights`` or with ``init_random_(..., init_seed + 2)``."""
+        if hasattr(self.vae, "decode"):
+            return self.vae
+        if not self._vae_self_built:
+            raise RuntimeError("guidance_eval needs a VAE with a decoder (pass vae=<object with .decode>); the supplied VAE "
+                               "has the encoder half only")
+        if not self._own_decoder:
+            self._own_decoder = (_build_decoder(self.device, self.weights_dtype, self.cfg.vae_weights, self.cfg.init_seed + 2,
+                                                self.cfg.enable_channels_last_format),)
+        return self._own_decoder[0]
+
     def decode_latents(self, latents, latent_height: int = 64, latent_width: int = 64):
-        """latents -> [B, 3, 8 h, 8 w] image in [0, 1] (:170-183).  The VAE DECODER is not part of the per-iteration path and
-        not restated in sd21: a VAE object that has ``decode`` (e.g. diffusers' AutoencoderKL) must be supplied."""
-        if not hasattr(self.vae, "decode"):
-            raise RuntimeError("guidance_eval needs a VAE with a decoder (pass vae=<object with .decode>); the restated "
-                               "AutoencoderKLEncoder has the encoder half only")
+        """latents -> [B, 3, 8 h, 8 w] image in [0, 1] (:170-183).  The restated decoder (sd21) runs its fused
+        stem / head path (decode_to_image); any other VAE object with ``decode`` runs the reference's expression."""
+        vae = self._decoder_vae()
         input_dtype = latents.dtype
         latents = F.interpolate(latents, (latent_height, latent_width), mode="bilinear", align_corners=False)
-        latents = 1 / self.vae.config.scaling_factor * latents
-        image = self.vae.decode(latents.to(self.weights_dtype)).sample
+        if isinstance(vae, sd21._VAEDecoderMixin):
+            return vae.decode_to_image(latents).to(input_dtype)
+        latents = 1 / vae.config.scaling_factor * latents
+        image = vae.decode(latents.to(self.weights_dtype)).sample
         image = (image * 0.5 + 0.5).clamp(0, 1)
         return image.to(input_dtype)
 
@@ -465,6 +481,22 @@ class StableDiffusionGuidance(nn.Module):
             self.grad_clip_val = C(self.cfg.grad_clip, epoch, global_step)
         self.set_min_max_steps(min_step_percent=C(self.cfg.min_step_percent, epoch, global_step),
                                max_step_percent=C(self.cfg.max_step_percent, epoch, global_step))
+
+
+def _build_decoder(device, dtype, weights: Optional[str], seed: int, channels_last: bool = True):
+    """A frozen SD-2.1 VAE decoder half (sd21.AutoencoderKLDecoder) on ``device`` in ``dtype``: loaded from a diffusers VAE
+    safetensors file, or random-init with ``seed``."""
+    with torch.device(device):
+        dec = sd21.AutoencoderKLDecoder()
+    if weights:
+        sd21.load_diffusers_weights(dec, weights)
+    else:
+        sd21.init_random_(dec, seed)
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    dec = dec.to(device=device, dtype=dtype).to(memory_format=fmt).eval()
+    for p in dec.parameters():
+        p.requires_grad_(False)
+    return dec
 
 
 def perpendicular_component(x, y):

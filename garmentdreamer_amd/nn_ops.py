@@ -131,6 +131,11 @@ SIGNATURES = {
     "gd_nn_lora_colreduce_group_desc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, C.POINTER(C.c_int)]),
     "gd_nn_lora_colreduce_group_launch": (_i, [_vp, _vp, _i, _i, _i, _i]),
     "gd_nn_lora_last_error": (C.c_char_p, []),
+    "gd_nn_vae_decoder_stem_supported": (_i, [_i, _i, _i, _i]),
+    "gd_nn_vae_decoder_stem": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "gd_nn_vae_decoder_head_supported": (_i, [_i, _i, _i, _i, _i]),
+    "gd_nn_vae_decoder_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "gd_nn_vae_decoder_last_error": (C.c_char_p, []),
     "gd_nn_last_error": (C.c_char_p, []),
 }
 
@@ -1624,6 +1629,101 @@ def vae_prologue_supported(x) -> bool:
 def vae_prologue(x, OH: int = 512, OW: int = 512):
     """x: planar fp32 [N,3,H,W] in [0,1] -> bf16 channels_last [N,3,OH,OW] = 2 * bilinear(x) - 1."""
     return _VaePrologue.apply(x, OH, OW)
+
+
+# ---------------------------------------------------------------------------------------------
+# VAE decoder ends (csrc/nn_vae_decoder.hip): the stem (latents -> post_quant_conv -> conv_in) and the head
+# (GroupNorm + SiLU -> conv_out [-> image]); forward only, no autograd node
+# ---------------------------------------------------------------------------------------------
+VAE_HEAD_RAW, VAE_HEAD_IMAGE = 0, 1
+_HEAD_MODES = {"raw": VAE_HEAD_RAW, "image": VAE_HEAD_IMAGE}
+
+
+def _frozen_bf16(*ts) -> bool:
+    return all(t is None or (t.is_cuda and t.dtype == torch.bfloat16 and not t.requires_grad) for t in ts)
+
+
+def vae_decode_stem_supported(latents, pq_weight, pq_bias, weight, bias) -> bool:
+    """latents [N, 4, h, w] fp32 / bf16 on the GPU, frozen bf16 post_quant_conv (4 -> 4, 1x1) and conv_in (4 -> Cout, 3x3)
+    with Cout % 64 == 0 up to 512, and no gradient asked of the result."""
+    if not (latents.is_cuda and latents.dim() == 4 and latents.shape[1] == 4 and latents.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    if torch.is_grad_enabled() and latents.requires_grad:
+        return False
+    if not (_frozen_bf16(pq_weight, pq_bias, weight, bias) and tuple(pq_weight.shape) == (4, 4, 1, 1)
+            and weight.dim() == 4 and tuple(weight.shape[1:]) == (4, 3, 3)):
+        return False
+    N, _, h, w = latents.shape
+    return bool(lib().gd_nn_vae_decoder_stem_supported(N, h, w, weight.shape[0]))
+
+
+def vae_decode_stem(latents, inv_scale: float, pq_weight, pq_bias, weight, bias):
+    """``conv_in(post_quant_conv(latents * inv_scale))`` -> bf16 channels_last [N, Cout, h, w] in one launch (fp32
+    accumulation, zero padding of the post-quant tensor).  Elsewhere the PyTorch ops of the same expression run in the
+    weights' dtype."""
+    if vae_decode_stem_supported(latents, pq_weight, pq_bias, weight, bias):
+        lat = latents.contiguous()
+        N, _, h, w = lat.shape
+        Cout = weight.shape[0]
+        wc = weight.contiguous(memory_format=torch.channels_last)
+        y = torch.empty((N, Cout, h, w), dtype=torch.bfloat16, device=lat.device, memory_format=torch.channels_last)
+        with torch.cuda.device(lat.device):
+            _check(lib().gd_nn_vae_decoder_stem(torch.cuda.current_stream(lat.device).cuda_stream, lat.data_ptr(),
+                                                int(lat.dtype == torch.bfloat16), float(inv_scale),
+                                                pq_weight.contiguous().data_ptr(),
+                                                None if pq_bias is None else pq_bias.contiguous().data_ptr(), wc.data_ptr(),
+                                                None if bias is None else bias.contiguous().data_ptr(), y.data_ptr(), N, h, w,
+                                                Cout), "gd_nn_vae_decoder_stem", "gd_nn_vae_decoder_last_error")
+        return y
+    _note_fallback("vae_decode_stem", weight, "needs [N, 4, h, w] fp32/bf16 GPU latents, frozen bf16 weights, Cout % 64 == 0 <= 512")
+    z = (latents * inv_scale).to(weight.dtype)
+    return F.conv2d(F.conv2d(z, pq_weight, pq_bias), weight, bias, padding=1)
+
+
+def vae_decode_head_supported(x, norm_weight, norm_bias, groups: int, weight, bias) -> bool:
+    """x bf16 [N, C, H, W] on the GPU (C % 64 == 0 up to 256), frozen bf16 GroupNorm affine and conv_out (C -> 3, 3x3), no
+    gradient asked of the result."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4) or (torch.is_grad_enabled() and x.requires_grad):
+        return False
+    if not (_frozen_bf16(norm_weight, norm_bias, weight, bias) and weight.dim() == 4
+            and tuple(weight.shape) == (3, x.shape[1], 3, 3) and norm_weight.numel() == x.shape[1]):
+        return False
+    N, C, H, W = x.shape
+    return bool(lib().gd_nn_vae_decoder_head_supported(N, H, W, C, int(groups)))
+
+
+def vae_decode_head(x, norm_weight, norm_bias, groups: int, eps: float, weight, bias, mode: str = "image", mean_rstd=None):
+    """``conv_out(silu(group_norm(x)))`` in one launch.  ``mode="raw"``: the convolution result ([-1, 1] convention of
+    diffusers' ``decode(z).sample``) in bf16; ``mode="image"``: ``clamp(r * 0.5 + 0.5, 0, 1)`` in fp32.  Either way a
+    channels_last [N, 3, H, W] tensor, i.e. the NCHW view of a contiguous NHWC [N, H, W, 3] buffer.  ``mean_rstd``:
+    [N * groups * 2] fp32 statistics of x if a producer already has them, else one statistics pass runs first."""
+    m = _HEAD_MODES[mode]
+    if vae_decode_head_supported(x, norm_weight, norm_bias, groups, weight, bias):
+        x = x.contiguous(memory_format=torch.channels_last)
+        N, C, H, W = x.shape
+        L = lib()
+        out = torch.empty((N, 3, H, W), dtype=torch.bfloat16 if m == VAE_HEAD_RAW else torch.float32, device=x.device,
+                          memory_format=torch.channels_last)
+        wc = weight.contiguous(memory_format=torch.channels_last)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            if mean_rstd is None:
+                mean_rstd = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
+                _check(L.gd_nn_groupnorm_stats(stream, x.data_ptr(), N, H * W, C, groups, float(eps),
+                                               _gn_workspace(x, N, groups).data_ptr(), mean_rstd.data_ptr()),
+                       "gd_nn_groupnorm_stats")
+            elif mean_rstd.dtype != torch.float32 or mean_rstd.numel() != N * groups * 2 or not mean_rstd.is_contiguous():
+                raise ValueError("vae_decode_head: mean_rstd must be contiguous fp32 [N * groups * 2]")
+            _check(L.gd_nn_vae_decoder_head(stream, x.data_ptr(), mean_rstd.data_ptr(), norm_weight.contiguous().data_ptr(),
+                                            norm_bias.contiguous().data_ptr(), int(groups), wc.data_ptr(),
+                                            None if bias is None else bias.contiguous().data_ptr(), out.data_ptr(), m, N, H,
+                                            W, C), "gd_nn_vae_decoder_head", "gd_nn_vae_decoder_last_error")
+        return out
+    _note_fallback("vae_decode_head", x, "needs bf16 GPU activations with C % 64 == 0 <= 256 and frozen bf16 C -> 3 weights")
+    r = F.conv2d(F.silu(F.group_norm(x, groups, norm_weight, norm_bias, eps)), weight, bias, padding=1)
+    if m == VAE_HEAD_RAW:
+        return r
+    return (r.float() * 0.5 + 0.5).clamp(0, 1).contiguous(memory_format=torch.channels_last)
 
 
 class _SparsityHead(torch.autograd.Function):

@@ -423,6 +423,32 @@ int gd_nn_lora_colreduce_group_desc(void* entry, const void* dy, const float* hs
 int gd_nn_lora_colreduce_group_launch(void* stream, const void* table_host, int n_entries, int grid1_x, int grid1_y, int grid2_x);
 const char* gd_nn_lora_last_error(void);
 
+/* The two ends of the SD-2.1 VAE decoder (diffusers AutoencoderKL.decode; csrc/nn_vae_decoder.hip).  Forward only.
+ *
+ * Stem, one launch:  y = conv_in(post_quant_conv(latents * inv_scale)), conv_in 3x3 / pad 1 with bias, 4 -> Cout.
+ *   latents: NCHW-contiguous [N, 4, h, w], fp32 (latents_bf16 = 0) or bf16 (1); pq_weight: bf16 [4][4] (post_quant_conv's
+ *   [4, 4, 1, 1] weight), pq_bias: bf16 [4] or NULL; weight: bf16 [Cout][3][3][4] (channels_last storage of conv_in.weight),
+ *   bias: bf16 [Cout] or NULL; y: bf16 NHWC [N, h, w, Cout].  Zero padding applies to the post-quant tensor (as in the
+ *   reference), fp32 accumulation.  Cout % 64 == 0, 64 <= Cout <= 512. */
+int gd_nn_vae_decoder_stem_supported(int N, int h, int w, int Cout);
+int gd_nn_vae_decoder_stem(void* stream, const void* latents, int latents_bf16, float inv_scale, const void* pq_weight,
+                           const void* pq_bias, const void* weight, const void* bias, void* y, int N, int h, int w, int Cout);
+
+/* Head, one launch:  r = conv_out(silu(GroupNorm_G(x))), conv_out 3x3 / pad 1 with bias, C -> 3.
+ *   x: bf16 NHWC [N, H, W, C]; mean_rstd: [N][G][2] = {mean, 1 / sqrt(var + eps)} (gd_nn_groupnorm_stats or a producer's
+ *   epilogue statistics); gamma, beta: bf16 [C]; weight: bf16 [3][3][3][C] (channels_last storage of conv_out.weight),
+ *   16-byte aligned; bias: bf16 [3] or NULL.  The normalised activation is rounded to bf16 before the convolution (as the
+ *   eager bf16 ops round it), accumulation in fp32.
+ *   mode GD_NN_VAE_HEAD_RAW:   out = bf16 NHWC [N, H, W, 3], r itself (diffusers' decode(z).sample, [-1, 1] convention);
+ *   mode GD_NN_VAE_HEAD_IMAGE: out = fp32 NHWC [N, H, W, 3], clamp(r * 0.5 + 0.5, 0, 1).
+ *   C % 64 == 0, 64 <= C <= 256, C % G == 0.  Every output element is written once, no atomics: bit-identical reruns. */
+#define GD_NN_VAE_HEAD_RAW 0
+#define GD_NN_VAE_HEAD_IMAGE 1
+int gd_nn_vae_decoder_head_supported(int N, int H, int W, int C, int G);
+int gd_nn_vae_decoder_head(void* stream, const void* x, const float* mean_rstd, const void* gamma, const void* beta, int G,
+                           const void* weight, const void* bias, void* out, int mode, int N, int H, int W, int C);
+const char* gd_nn_vae_decoder_last_error(void);
+
 const char* gd_nn_last_error(void);
 
 #ifdef __cplusplus
