@@ -17,43 +17,18 @@
 #include <stdlib.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 
 namespace {
 
-thread_local char g_err[256] = "";
+using namespace gdnn;
+
 #ifndef GD_ATTN_ABLATE
 #define GD_ATTN_ABLATE 0   // timing builds only (tools/attn_ablate.sh): 1 no exp2, 2 no LDS-DMA after the prologue, 3 no MFMA, 4 no LDS fragment reads, 5 no running-maximum pass, 6 no per-tile barrier, 9 / 10 orders of the loop head
 #endif
 int g_attn_waves = 0;   // GD_NN_ATTN_WAVES = 4 / 8 forces the workgroup size (tuning)
 int g_attn_xcd = 1;     // GD_NN_ATTN_XCD=0: query tiles dealt round-robin over the XCDs (A/B)
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi)
-{
-    f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
-// byte offset of logical (row, 16-B chunk j) inside a swizzled [rows][64] bf16 tile image (256-byte lines)
-__device__ __forceinline__ int swz(int row, int j)
-{
-    return (row >> 1) * 256 + (((((row & 1) << 3) | j) ^ ((row >> 1) & 15)) << 4);
-}
-
-__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, char* lds_wave_base)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff,
-                                             0, 0);
-}
 
 constexpr int kTk = 64, kD = 64;
 constexpr int kTile = kTk * kD * 2;   // 8 KB
@@ -144,10 +119,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_fwd_d64_kernel(const uint1
     }
     // K rows: [key][64 d], row stride k_rs elements; Vt rows: [d][Skv]
     const uint32_t k_row_bytes = (uint32_t)k_rs * 2u, v_row_bytes = (uint32_t)Skv * 2u;
-    const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(k + b * k_bs + h * kD), 0, (int)((uint32_t)kv_len * k_row_bytes), 0x00020000);   // rows >= kv_len read as 0
-    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(vt + b * vt_bs + ((int64_t)h * kD) * Skv), 0, (int)((uint32_t)kD * v_row_bytes), 0x00020000);
+    // rows >= kv_len read as 0
+    const __amdgpu_buffer_rsrc_t rs_k = buffer_rsrc(k + b * k_bs + h * kD, (uint32_t)kv_len * k_row_bytes);
+    const __amdgpu_buffer_rsrc_t rs_v = buffer_rsrc(vt + b * vt_bs + ((int64_t)h * kD) * Skv, (uint32_t)kD * v_row_bytes);
     uint32_t k_off[NP], v_off[NP];
 #pragma unroll
     for (int i = 0; i < NP; i++) {
@@ -424,10 +398,11 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_d64_kernel(
     if (MODE == 0) { Lr = lse[stat_base + rld] * log2e; Dr = dsum[stat_base + rld]; }
 
     const uint32_t x1_row = (uint32_t)x1_rs * 2u, x2_row = (uint32_t)x2_rs * 2u, t_row = (uint32_t)Sc * 2u;
-    const __amdgpu_buffer_rsrc_t rs_x1 = __builtin_amdgcn_make_buffer_rsrc((void*)(x1 + b * x1_bs + h * kD), 0, (int)((uint32_t)c_len * x1_row), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)(x2 + b * x2_bs + h * kD), 0, (int)((uint32_t)c_len * x2_row), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_t1 = __builtin_amdgcn_make_buffer_rsrc((void*)(t1 + (((int64_t)b * H + h) * kD) * Sc), 0, (int)((uint32_t)kD * t_row), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_t2 = __builtin_amdgcn_make_buffer_rsrc((void*)((MODE == 1 ? t2 : t1) + (((int64_t)b * H + h) * kD) * Sc), 0, (int)((uint32_t)kD * t_row), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x1 = buffer_rsrc(x1 + b * x1_bs + h * kD, (uint32_t)c_len * x1_row);
+    const __amdgpu_buffer_rsrc_t rs_x2 = buffer_rsrc(x2 + b * x2_bs + h * kD, (uint32_t)c_len * x2_row);
+    const __amdgpu_buffer_rsrc_t rs_t1 = buffer_rsrc(t1 + (((int64_t)b * H + h) * kD) * Sc, (uint32_t)kD * t_row);
+    const __amdgpu_buffer_rsrc_t rs_t2 =
+        buffer_rsrc((MODE == 1 ? t2 : t1) + (((int64_t)b * H + h) * kD) * Sc, (uint32_t)kD * t_row);
     uint32_t a_off[NP], b_off[NP], t_off[NP];
 #pragma unroll
     for (int i = 0; i < NP; i++) {
@@ -649,9 +624,7 @@ static int launch_attention(hipStream_t s, const void* q, const void* k, const v
         hipLaunchKernelGGL(attn_fwd_d64_kernel<4>, dim3((S + 127) / 128, B * H), dim3(256), 6 * kTile, s, (const uint16_t*)q,
                            (const uint16_t*)k, (const uint16_t*)vt, (uint16_t*)o, S, Skv, H, q_bs, q_rs, k_bs, k_rs, o_bs,
                            o_rs, c, kv_len, lse, vt_bs, g_attn_xcd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 static int check_attention(const void* q, const void* k, const void* v, const void* o, int B, int S, int Skv, int H, int q_rs,
@@ -776,9 +749,7 @@ int gd_nn_attention_d64_backward(void* stream, const void* q, const void* k, con
                            (const uint16_t*)dout, do_bs, do_rs, dot, qt, lse, dsum, (uint16_t*)dv, dv_bs, dv_rs, (uint16_t*)dk,
                            dk_bs, dk_rs, kv_len, S, H, c, scale, kv_len, S, S, 0, (float*)nullptr);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -34,6 +34,8 @@
 #include <vector>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 
 #ifndef GD_CONV_ABLATE
 #define GD_CONV_ABLATE 0
@@ -41,8 +43,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+using namespace gdnn;
 
 // Timing-only switches of tools/nn_variants.sh (never defined in a product build):
 //   GD_PATCH_EPI=1  the patch-staged kernels skip their epilogue stores (wrong results; the condition is never true at
@@ -55,47 +56,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int BK = 64;    // channels of one tap per K-step (128-byte rows)
-
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-// two fp32 -> packed bf16 (round to nearest even) in ONE instruction: v_cvt_pk_bf16_f32 (gfx950)
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi)
-{
-    f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// byte offset of logical (row, 16-B chunk j) inside a swizzled [rows][64] bf16 tile image
-__device__ __forceinline__ int swz(int row, int j)
-{
-    return (row >> 1) * 256 + (((((row & 1) << 3) | j) ^ ((row >> 1) & 15)) << 4);
-}
-
-__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff,
-                                            char* lds_wave_base)
-{
-    // buffer_load_dwordx4 ... offen lds: 16 B per lane straight into LDS (wave-uniform base +
-    // lane*16); a lane whose voffset is beyond num_records gets ZEROS -- that is the halo padding
-    // and the ragged-tile masking, with no branch and no zero page.
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff,
-                                             soff, 0, 0);
-}
-
-constexpr uint32_t kOOB = 0x80000000u;   // voffset that fails the buffer range check (tensors are < 2 GiB)
 
 // Geometry of one implicit-GEMM launch.  GEMM row m = (image n, grid point (a, b)) on an Hg x Wg grid; its
 // K dimension walks `ntaps` taps x Cin channels, tap t reading input pixel (a*sy + ty[t], b*sx + tx[t]) (zero
@@ -146,10 +106,8 @@ __device__ __forceinline__ void conv3x3_nhwc_bf16_body(
     // before `in`.
     const uint32_t row_bytes = (uint32_t)Cin * 2u;
     const uint32_t back = (uint32_t)g.back * row_bytes;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)in - back), 0, (int)((uint32_t)Nimg * (uint32_t)(H * W) * row_bytes + back), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)wt, 0, (int)((uint32_t)Cout * (uint32_t)g.wtaps * row_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buffer_rsrc((const char*)in - back, (uint32_t)Nimg * (uint32_t)(H * W) * row_bytes + back);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(wt, (uint32_t)Cout * (uint32_t)g.wtaps * row_bytes);
 
     // LDS image: 256-byte lines = two consecutive 128-byte tile rows = 16 slots of 16 B; logical
     // slot c = (row&1)*8 + chunk is stored at slot c ^ (line & 15): a 64-lane fragment read then
@@ -561,10 +519,8 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
     const int n0 = tn * BN;
 
     const uint32_t row_bytes = (uint32_t)Cin * 2u;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)in, 0, (int)((uint32_t)Nimg * (uint32_t)(H * W) * row_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)wt, 0, (int)((uint32_t)Cout * 9u * row_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buffer_rsrc(in, (uint32_t)Nimg * (uint32_t)(H * W) * row_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(wt, (uint32_t)Cout * 9u * row_bytes);
 
     // ---- activation loader: thread <-> fixed channel octet (tid & 7), NA patch pixels
     const int a_chunk = tid & 7;
@@ -792,10 +748,8 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
     };
 
     const uint32_t row_bytes = (uint32_t)Cin * 2u;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)in, 0, (int)((uint32_t)Nimg * (uint32_t)(H * W) * row_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)wt, 0, (int)((uint32_t)Cout * 9u * row_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buffer_rsrc(in, (uint32_t)Nimg * (uint32_t)(H * W) * row_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(wt, (uint32_t)Cout * 9u * row_bytes);
 
     // ---- activation loader: thread <-> fixed channel octet (tid & 7), NA patch pixels
     const int a_chunk = tid & 7;
@@ -1315,13 +1269,6 @@ struct ConvProf {
     }
 } g_cprof;
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1483,9 +1430,7 @@ static int launch_conv(hipStream_t s, const void* x, const void* weight, const v
         g_cprof.total_bytes += 2.0 * ((double)N * g.Hin * g.Win * Cin + (double)g.ntaps * Cin * Cout + (double)M * Cout +
                                       (residual ? (double)M * Cout : 0.0));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 static void add_tap(ConvGeom& g, int dy, int dx, int widx)
@@ -1731,9 +1676,7 @@ static int launch_patch(void* stream, const void* x, const float* mean_rstd, con
         g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
                                       (residual ? (double)M * Cout : 0.0));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_gn_forward(void* stream, const void* x, const float* mean_rstd, const void* gamma, const void* beta,
@@ -1787,9 +1730,7 @@ int gd_nn_conv3x3_wino_weights(void* stream, const void* weight, void* u, int Co
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(conv3x3_wino_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)weight,
                        (uint16_t*)u, Cout, Cin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_wino_supported(int N, int H, int W, int Cin, int Cout)
@@ -1848,9 +1789,7 @@ static int launch_wino(void* stream, const void* x, const float* mean_rstd, cons
         g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
                                       (residual ? (double)M * Cout : 0.0));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_wino_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,
@@ -1883,9 +1822,7 @@ int gd_nn_conv3x3_wide_weights(void* stream, const void* weight, void* u, int Co
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(conv3x3_wide_weights_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)weight,
                        (uint16_t*)u, Cout, Cin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 #ifdef GD_NN_EXPERIMENTAL_STREAM   // tools/stream_variants.sh only: a measured negative, not in libgd_nn.so
@@ -1946,9 +1883,7 @@ static int launch_wide(void* stream, const void* x, const float* mean_rstd, cons
         g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
                                       (residual ? (double)M * Cout : 0.0));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_wide_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,
@@ -2021,9 +1956,7 @@ static int first_forward(void* stream, const void* x, const void* weight, const 
         else if (Cin == 3) GD_FIRST_M(3);
         else GD_FIRST_M(4);
 #undef GD_FIRST_M
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-        return GD_NN_OK;
+        return launch_status();
     }
     const int octs = Cout / 8, gpb = 256 / octs;
     const int64_t groups = (int64_t)N * H * ((W + 3) / 4);
@@ -2041,9 +1974,7 @@ static int first_forward(void* stream, const void* x, const void* weight, const 
     else if (Cin == 3) GD_FIRST(3);
     else GD_FIRST(4);
 #undef GD_FIRST
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 static ConvGeom s2_forward_geom(int Hin, int Win, int pad_lo)
@@ -2274,9 +2205,7 @@ int gd_nn_conv3x3_first_dgrad_weights(void* stream, const void* weight, void* wp
     if (Cout != 128 || Cin < 1 || Cin > 3) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_first_dgrad: need Cout == 128 and 1 <= Cin <= 3");
     hipLaunchKernelGGL(conv3x3_first_dgrad_weights_kernel, dim3(16), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)weight,
                        (uint16_t*)wpack, Cin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_first_dgrad(void* stream, const void* dy, const void* wpack, void* dx4, int N, int H, int W, int Cin, int Cout)
@@ -2287,9 +2216,7 @@ int gd_nn_conv3x3_first_dgrad(void* stream, const void* dy, const void* wpack, v
     const int tx = (W + 15) / 16, ty = (H + 15) / 16;
     hipLaunchKernelGGL(conv3x3_first_dgrad_kernel, dim3((unsigned)(N * tx * ty)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)dy, (const uint16_t*)wpack, (uint16_t*)dx4, H, W, tx, ty);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_flip_weights(void* stream, const void* weight, void* flipped, int Cout, int Cin)
@@ -2297,9 +2224,7 @@ int gd_nn_conv3x3_flip_weights(void* stream, const void* weight, void* flipped, 
     if (!weight || !flipped) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
     hipLaunchKernelGGL(conv3x3_flip_weights_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)weight, (uint16_t*)flipped, Cout, Cin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 }  // extern "C"

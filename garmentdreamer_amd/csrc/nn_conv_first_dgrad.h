@@ -12,6 +12,8 @@
 // whole by one wave within eight back-to-back loads) goes to LDS in fp32, then every thread sums the nine shifted entries of its
 // pixel in fp32: one rounding to bf16 (the implicit-GEMM form rounded nothing either; same accuracy class, fewer terms per sum).
 // HBM: 1.27x dy (halo) + 8 B per pixel out.
+#pragma once
+#include "nn_device.h"   // (already in at file scope: nn_conv3x3.hip includes it before opening its namespace)
 
 namespace {
 
@@ -47,8 +49,7 @@ __global__ __launch_bounds__(256) void conv3x3_first_dgrad_kernel(const uint16_t
 #pragma unroll
     for (int kk = 0; kk < 8; kk++) wf[kk] = *(const bf16x8_t*)(wp + fn * 128 + 16 * kk + 8 * fh);
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(dy + (size_t)n * H * W * 128), 0,
-                                                                        (int)((uint32_t)H * (uint32_t)W * 256u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(dy + (size_t)n * H * W * 128, (uint32_t)H * (uint32_t)W * 256u);
     for (int b = wave; b < kFdBlocks; b += 4) {
         const int hp = 32 * b + fn;
         const int hy = hp / kFdHalo, hx = hp - hy * kFdHalo;

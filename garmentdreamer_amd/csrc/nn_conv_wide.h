@@ -21,6 +21,7 @@
 // GN = true: conv(silu(GroupNorm(x))) of diffusers' ResnetBlock2D -- the raw patch chunk goes global -> registers ->
 // x * a[n, c] + b[n, c] -> SiLU -> bf16 -> LDS (a = gamma * rstd, b = beta - mean * a; zero padding after the transform).
 #pragma once
+#include "nn_device.h"   // (already in at file scope: nn_conv3x3.hip includes it before opening its namespace)
 
 constexpr int kWideCK = 32;
 constexpr int kWidePW = 34, kWidePix = 18 * kWidePW;          // 16 x 32 tile + halo = 612 patch pixels
@@ -78,11 +79,9 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
     const int n0 = tn * 128;
 
     const uint32_t row_bytes = (uint32_t)Cin * 2u;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)in, 0, (int)((uint32_t)Nimg * (uint32_t)(H * W) * row_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buffer_rsrc(in, (uint32_t)Nimg * (uint32_t)(H * W) * row_bytes);
     const int kc = Cin / kWideCK;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)uw, 0, (int)((uint32_t)tiles_n * 3u * (uint32_t)kc * (uint32_t)kWideWStage), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(uw, (uint32_t)tiles_n * 3u * (uint32_t)kc * (uint32_t)kWideWStage);
 
     // ---- patch loader: piece q = tid + 512 i -> patch pixel q >> 2, 16-byte chunk slot q & 3 (the lane fetches the channel
     // octet that belongs there: swizzle on the source side, the LDS image of an LDS-DMA is lane linear)

@@ -35,6 +35,7 @@
 //      quarter read four different chunks, for every ky shift
 //   W: (pos * 128 + co) * 64, key = (co >> 2) & 3; filled by LDS-DMA with the key applied on the source side.
 #pragma once
+#include "nn_device.h"   // (already in at file scope: nn_conv3x3.hip includes it before opening its namespace)
 
 // Timing-only switches of tools/wino_ablate.sh (never defined in a product build; results are wrong by construction):
 //   1 no input transform   2 no filter DMA after the first slice   3 no patch DMA after the first chunk
@@ -48,6 +49,15 @@ constexpr int kWinoVStage = 4 * 18 * 8 * kWinoCK * 2;         // 36864
 constexpr int kWinoWStage = 4 * 128 * kWinoCK * 2;            // 32768
 constexpr int kWinoPBytes = 21 * 1024;                        // 336 pixel rows of 64 B (324 used)
 constexpr int kWinoLds = 2 * kWinoVStage + 2 * kWinoWStage + kWinoPBytes;   // 160768
+
+// fp32 -> bf16, round to nearest even, WITHOUT nn_device.h's NaN guard: for the finite sums of the weight transform
+// below, its only caller.  Kept apart from f2bf so that conv3x3_wino_weights_kernel keeps its instructions.
+__device__ __forceinline__ uint16_t f2bf_finite(float f)
+{
+    uint32_t u = __float_as_uint(f);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
 
 // w [Cout][3][3][Cin] bf16 -> the transformed filter bank in the ORDER THE KERNEL STREAMS IT: for every (128-channel
 // block tn, ky, 32-channel chunk c) one contiguous 32 KB slice = the LDS image of that step,
@@ -78,7 +88,7 @@ __global__ __launch_bounds__(256) void conv3x3_wino_weights_kernel(const uint16_
                 const uint16_t* g = w + ((size_t)co * 3 + ky) * 3 * Cin + ci0 + e;
                 const float g0 = bf2f(g[0]), g1 = bf2f(g[Cin]), g2 = bf2f(g[2 * Cin]);
                 v = pos == 0 ? g[0] : pos == 3 ? g[2 * Cin]
-                    : pos == 1 ? f2bf(0.5f * ((g0 + g2) + g1)) : f2bf(0.5f * ((g0 + g2) - g1));
+                    : pos == 1 ? f2bf_finite(0.5f * ((g0 + g2) + g1)) : f2bf_finite(0.5f * ((g0 + g2) - g1));
             }
             o[e] = v;
         }
@@ -123,11 +133,9 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(
     const int n0 = tn * BN;
 
     const uint32_t row_bytes = (uint32_t)Cin * 2u;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)in, 0, (int)((uint32_t)Nimg * (uint32_t)(H * W) * row_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buffer_rsrc(in, (uint32_t)Nimg * (uint32_t)(H * W) * row_bytes);
     const int kc = Cin / kWinoCK;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)uw, 0, (int)((uint32_t)tiles_n * 3u * (uint32_t)kc * (uint32_t)kWinoWStage), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(uw, (uint32_t)tiles_n * 3u * (uint32_t)kc * (uint32_t)kWinoWStage);
 
     // ---- raw patch loader (LDS-DMA): piece q = tid + 512 i -> pixel q >> 2, 16-byte chunk q & 3
     uint32_t p_goff[3];

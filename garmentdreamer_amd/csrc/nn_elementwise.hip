@@ -17,31 +17,18 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 #include "nn_math.h"
 
 namespace {
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
+using namespace gdnn;
 
-struct alignas(16) bf16x8 {
-    uint16_t v[8];
-};
-
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-// Packed fp32 helpers: these row passes are VALU-bound on MI355X (a wave64 VALU instruction holds its SIMD ~4.5 cycles,
-// tools/probes/valu_rate_probe.hip; SQ_INSTS_VALU x 4.5 cycles = the whole kernel time in profiles/r02_pmc.json), so two
-// channels share every arithmetic instruction (v_pk_*_f32) and bf16 rounding is v_cvt_pk_bf16_f32 (nearest even).
-using gdnn::f2;
-using gdnn::unpack2;
-using gdnn::pack2;
-using gdnn::round_bf16;
-using gdnn::erf_as2;
-struct alignas(16) u32x4 { uint32_t w[4]; };
+// Packed fp32 helpers (nn_device.h, nn_math.h): these row passes are VALU-bound on MI355X (a wave64 VALU instruction holds
+// its SIMD ~4.5 cycles, tools/probes/valu_rate_probe.hip; SQ_INSTS_VALU x 4.5 cycles = the whole kernel time in
+// profiles/r02_pmc.json), so two channels share every arithmetic instruction (v_pk_*_f32) and bf16 rounding is
+// v_cvt_pk_bf16_f32 (nearest even).
 
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -226,8 +213,6 @@ __global__ __launch_bounds__(256) void layernorm_backward_kernel(const bf16x8* _
     }
 }
 
-}  // namespace
-
 // Row softmax of the VAE mid block's single-head attention ([8 images x 4096 queries] rows of 4096 bf16 scores, 268 MB: the
 // score matrix is materialised on purpose) and its backward.  One wave per row, the row in registers (R 16-byte
 // vectors per lane): forward = read once, write once (in place if y == x); backward ds = p (dp - sum(p dp)) = read p and dp once,
@@ -358,6 +343,8 @@ __global__ __launch_bounds__(256) void conv1x1_c8_kernel(const u32x4* __restrict
     }
 }
 
+}  // namespace
+
 extern "C" {
 
 const char* gd_nn_elementwise_last_error(void) { return g_err; }
@@ -371,7 +358,7 @@ int gd_nn_geglu_forward(void* stream, const void* x, void* y, int64_t rows, int 
     const int grid = (int)(blocks < 16384 ? blocks : 16384);
     hipLaunchKernelGGL(geglu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x, (bf16x8*)y, nvec,
                        inner / 8);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "geglu: launch failed");
+    return launch_status("geglu: launch failed");
 }
 
 int gd_nn_add_layernorm_forward(void* stream, const void* x, const void* residual, const void* weight, const void* bias,
@@ -394,7 +381,7 @@ int gd_nn_add_layernorm_forward(void* stream, const void* x, const void* residua
     else if (vpl == 3) GD_LN(3);
     else GD_LN(4);
 #undef GD_LN
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "add_layernorm: launch failed");
+    return launch_status("add_layernorm: launch failed");
 }
 
 int gd_nn_geglu_backward(void* stream, const void* x, const void* dy, void* dx, int64_t rows, int inner)
@@ -406,7 +393,7 @@ int gd_nn_geglu_backward(void* stream, const void* x, const void* dy, void* dx, 
     const int grid = (int)(blocks < 16384 ? blocks : 16384);
     hipLaunchKernelGGL(geglu_backward_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16x8*)x, (const bf16x8*)dy,
                        (bf16x8*)dx, nvec, inner / 8);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "geglu_backward: launch failed");
+    return launch_status("geglu_backward: launch failed");
 }
 
 int gd_nn_layernorm_backward(void* stream, const void* s, const void* dy, const void* weight, const void* ds, void* dx,
@@ -425,7 +412,7 @@ int gd_nn_layernorm_backward(void* stream, const void* s, const void* dy, const 
     else if (vpl == 3) GD_LNB(3);
     else GD_LNB(4);
 #undef GD_LNB
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "layernorm_backward: launch failed");
+    return launch_status("layernorm_backward: launch failed");
 }
 
 int gd_nn_conv1x1_c8(void* stream, const void* x, const void* weight, const void* bias, void* y, int64_t npix, int transposed)
@@ -440,7 +427,7 @@ int gd_nn_conv1x1_c8(void* stream, const void* x, const void* weight, const void
     else
         hipLaunchKernelGGL(conv1x1_c8_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u32x4*)x,
                            (const uint16_t*)weight, (const uint16_t*)bias, (u32x4*)y, npix);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "conv1x1_c8: launch failed");
+    return launch_status("conv1x1_c8: launch failed");
 }
 
 int gd_nn_softmax_rows_forward(void* stream, const void* x, void* y, int64_t rows, int L)
@@ -456,7 +443,7 @@ int gd_nn_softmax_rows_forward(void* stream, const void* x, void* y, int64_t row
     else if (R <= 8) GD_SM(8);
     else GD_SM(16);
 #undef GD_SM
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "softmax_rows: launch failed");
+    return launch_status("softmax_rows: launch failed");
 }
 
 int gd_nn_softmax_rows_backward(void* stream, const void* p, const void* dp, void* ds, int64_t rows, int L)
@@ -472,7 +459,7 @@ int gd_nn_softmax_rows_backward(void* stream, const void* p, const void* dp, voi
     else if (R <= 8) GD_SMB(8);
     else GD_SMB(16);
 #undef GD_SMB
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "softmax_rows_backward: launch failed");
+    return launch_status("softmax_rows_backward: launch failed");
 }
 
 }  // extern "C"

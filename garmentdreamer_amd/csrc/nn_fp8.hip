@@ -25,44 +25,18 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 
 namespace {
 
+using namespace gdnn;
+
 typedef __attribute__((ext_vector_type(8))) int v8i;
 typedef __attribute__((ext_vector_type(4))) int v4i;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int BKB = 128;                 // bytes (= e4m3 channels) of one tap per K-step
-constexpr uint32_t kOOB = 0x80000000u;   // voffset that fails the buffer range check (tensors are < 2 GiB)
 constexpr int kUnitScale = 0x7f7f7f7f;   // E8M0 1.0 in every byte
-
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi)
-{
-    f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
-// byte offset of logical (row, 16-B chunk j) inside a swizzled [rows][128 B] tile image (as nn_conv3x3.hip)
-__device__ __forceinline__ int swz(int row, int j)
-{
-    return (row >> 1) * 256 + (((((row & 1) << 3) | j) ^ ((row >> 1) & 15)) << 4);
-}
-
-__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, char* lds_wave_base)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff,
-                                             0, 0);
-}
 
 struct TapGeom {          // subset of nn_conv3x3.hip's ConvGeom: stride 1, output grid = input grid
     int H, W, ntaps, back, wtaps;
@@ -94,10 +68,8 @@ __global__ __launch_bounds__(64 * WN * WM) void gemm_taps_fp8_kernel(
 
     const uint32_t row_a = (uint32_t)Cin, row_w = (uint32_t)CinP;
     const uint32_t back = (uint32_t)g.back * row_a;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)in - back), 0, (int)((uint32_t)Nimg * (uint32_t)HW * row_a + back), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)wt, 0, (int)((uint32_t)Cout * (uint32_t)g.wtaps * row_w), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buffer_rsrc((const char*)in - back, (uint32_t)Nimg * (uint32_t)HW * row_a + back);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(wt, (uint32_t)Cout * (uint32_t)g.wtaps * row_w);
 
     uint32_t a_off[NA];
     int a_y[NA], a_x[NA];
@@ -324,9 +296,7 @@ int launch(hipStream_t s, const void* x, const void* w, const void* bias, int bi
     else if (variant == 1) GD_LAUNCH8(128, 256, 2, 4);
     else GD_LAUNCH8(128, 128, 2, 2);
 #undef GD_LAUNCH8
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 void add_tap(TapGeom& g, int dy, int dx, int widx)
@@ -350,7 +320,7 @@ int gd_nn_fp8_quantize(void* stream, const void* x_bf16, void* y_fp8, int64_t n,
     const int64_t blocks = (nvec + 255) / 256;
     hipLaunchKernelGGL(quantize_fp8_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream,
                        (const uint4*)x_bf16, (uint2*)y_fp8, nvec, inv_scale);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "fp8 quantize: launch failed");
+    return launch_status("fp8 quantize: launch failed");
 }
 
 int gd_nn_fp8_pack_weights(void* stream, const void* w_bf16, void* w_fp8, int64_t rows, int K, int Kp, float inv_scale)
@@ -361,7 +331,7 @@ int gd_nn_fp8_pack_weights(void* stream, const void* w_bf16, void* w_fp8, int64_
     const int64_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(pack_weights_fp8_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0,
                        (hipStream_t)stream, (const uint16_t*)w_bf16, (uint8_t*)w_fp8, rows, K, Kp, inv_scale);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "fp8 pack_weights: launch failed");
+    return launch_status("fp8 pack_weights: launch failed");
 }
 
 int gd_nn_fp8_linear_forward(void* stream, const void* x_fp8, const void* w_fp8, const void* bias, const void* residual,

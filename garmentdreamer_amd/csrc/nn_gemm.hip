@@ -37,6 +37,8 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 #include "nn_math.h"
 
 // Timing-only switches of tools/gemm_variants.sh (never defined in a product build; results are wrong with any of them):
@@ -52,10 +54,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+using namespace gdnn;
 
 constexpr int kBK = 64;                    // K tile (128-byte rows)
 constexpr int kHalf = 128;                 // rows of a half tile
@@ -63,24 +62,7 @@ constexpr int kSlot = kHalf * kBK * 2;     // 16384 B
 constexpr int kSlots = 10;                 // W: slots 0..3 = [K-tile parity][half]; x: slots 4..9 = [K tile mod 3][half]
 constexpr int kLds = kSlots * kSlot;       // 163840 B = the CU's LDS
 constexpr int kThreads = 512;
-constexpr uint32_t kOOB = 0x80000000u;     // voffset that fails the buffer range check (every tensor here is < 2 GiB)
 
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi)
-{
-    f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, char* lds_wave_base)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff,
-                                             0, 0);
-}
-// byte offset of logical (row, 16-B chunk j) inside a swizzled [128][64] bf16 half-tile image (nn_conv3x3.hip's layout)
-__device__ __forceinline__ int swz(int row, int j)
-{
-    return (row >> 1) * 256 + (((((row & 1) << 3) | j) ^ ((row >> 1) & 15)) << 4);
-}
 
 // row offset + channel offset, out of range if either part is (kOOB + kOOB would wrap around to a valid address)
 __device__ __forceinline__ uint32_t addr2(uint32_t row_off, uint32_t ch_off)
@@ -122,10 +104,8 @@ __global__ __launch_bounds__(kThreads) void gemm256_kernel(const uint16_t* __res
 
     const uint32_t row_bytes = (uint32_t)K * 2u;
     const int w_rows = MODE == kModeGeglu ? 2 * N : N;
-    const __amdgpu_buffer_rsrc_t rs_w =
-        __builtin_amdgcn_make_buffer_rsrc((void*)w, 0, (int)((uint32_t)w_rows * row_bytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)((uint32_t)M * row_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = buffer_rsrc(w, (uint32_t)w_rows * row_bytes);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(x, (uint32_t)M * row_bytes);
 
     // loader: a half tile is 1024 16-byte chunks = 2 per thread; chunk q = tid + 512 i sits at LDS byte 16 q (lane-linear
     // DMA), and holds logical (row r, chunk c & 7) with line = q >> 4, c = (q & 15) ^ (line & 15), r = 2 line + (c >> 3)
@@ -215,8 +195,7 @@ __global__ __launch_bounds__(kThreads) void gemm256_kernel(const uint16_t* __res
         u32x2 rr[2][4][4];
         const bool with_res = MODE == kModeBias && residual != nullptr;
         if (with_res) {
-            const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)residual, 0, live ? (int)(uint32_t)((size_t)M * (size_t)ldy * 2u) : 0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_r = buffer_rsrc(residual, live ? (uint32_t)((size_t)M * (size_t)ldy * 2u) : 0u);
             const int m0 = tile_tm(tile) * 256 + (wp >> 1) * kHalf + (wp & 1) * 64;
 #pragma unroll
             for (int bb = 0; bb < 2; bb++) {
@@ -350,8 +329,7 @@ __global__ __launch_bounds__(kThreads) void gemm256_kernel(const uint16_t* __res
         {
             typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
             const int m0 = tile_tm(tile) * 256 + (wp >> 1) * kHalf + (wp & 1) * 64;
-            const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)y, 0, (int)(uint32_t)((size_t)M * (size_t)ldy * 2u), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_y = buffer_rsrc(y, (uint32_t)((size_t)M * (size_t)ldy * 2u));
             uint32_t row_off[2];
 #pragma unroll
             for (int bb = 0; bb < 2; bb++) {
@@ -387,12 +365,6 @@ __global__ __launch_bounds__(kThreads) void gemm256_kernel(const uint16_t* __res
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
 
 int num_cus()
 {
@@ -426,9 +398,7 @@ int launch(void* stream, const void* x, const void* w, const void* bias, const v
     if (ntiles < grid) grid = (int)((ntiles + 7) & ~7);
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(kThreads), kLds, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)w,
                        (const uint16_t*)bias, (const uint16_t*)residual, (uint16_t*)y, (int)M, K, N, ldy, tiles_n, (int)ntiles);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 }  // namespace

@@ -21,23 +21,12 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 
 namespace {
 
-thread_local char g_err[256] = "";
-
-struct alignas(16) bf16x8 {
-    uint16_t v[8];
-};
-
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);                                              // round to nearest even
-    return (uint16_t)(u >> 16);
-}
+using namespace gdnn;
 
 // ---- packed fp32 helpers.  Measured on MI355X (tools/probes/valu_rate_probe.hip): a wave64 VALU instruction holds
 // its SIMD ~4.5 cycles, so these "streaming" passes were VALU-bound, not HBM-bound (SQ_INSTS_VALU x 4.5 cycles = the
@@ -45,11 +34,6 @@ __device__ __forceinline__ uint16_t f2bf(float f)
 // software bf16 rounding per element and scalar fp32 arithmetic.  Here two channels share every arithmetic
 // instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32), the sigmoid is exp2 + v_rcp_f32 and the rounding is
 // v_cvt_pk_bf16_f32 (round to nearest even, the same bits as f2bf for every non-NaN input).
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-struct alignas(16) u32x4 { uint32_t w[4]; };
-__device__ __forceinline__ f2 unpack2(uint32_t w) { return f2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; }
-__device__ __forceinline__ uint32_t pack2(f2 v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2_t)); }
 __device__ __forceinline__ f2 sigmoid2(f2 z)
 {
     const f2 e = z * -1.44269504088896341f;
@@ -265,8 +249,8 @@ __global__ __launch_bounds__(THREADS) void gn_group_fused_kernel(const uint32_t*
     // image n as a buffer: 32-bit byte offsets (one VGPR per access instead of a 64-bit address pair), and an offset
     // past the end reads 0 / drops the store, so the ragged tail needs no branch
     const uint32_t img_bytes = (uint32_t)HW * (uint32_t)C2 * 4u;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)n * HW * C2), 0, (int)img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)(y + (size_t)n * HW * C2), 0, (int)img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(x + (size_t)n * HW * C2, img_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = buffer_rsrc(y + (size_t)n * HW * C2, img_bytes);
     const uint32_t goff = (uint32_t)g * (uint32_t)cg2 * 4u;
     uint32_t v[R];
     f2 s = f2{0.f, 0.f}, ss = f2{0.f, 0.f};
@@ -351,9 +335,9 @@ __global__ __launch_bounds__(THREADS) void gn_group_fused_bwd_kernel(const uint3
     const int n = bid / G, g = bid - n * G, tid = threadIdx.x;
     const int total = HW * cg2;
     const uint32_t img_bytes = (uint32_t)HW * (uint32_t)C2 * 4u;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (size_t)n * HW * C2), 0, (int)img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc((void*)(dy + (size_t)n * HW * C2), 0, (int)img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc((void*)(dx + (size_t)n * HW * C2), 0, (int)img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(x + (size_t)n * HW * C2, img_bytes);
+    const __amdgpu_buffer_rsrc_t rs_d = buffer_rsrc(dy + (size_t)n * HW * C2, img_bytes);
+    const __amdgpu_buffer_rsrc_t rs_o = buffer_rsrc(dx + (size_t)n * HW * C2, img_bytes);
     const uint32_t goff = (uint32_t)g * (uint32_t)cg2 * 4u;
     const float mean = mean_rstd[((size_t)n * G + g) * 2], rstd = mean_rstd[((size_t)n * G + g) * 2 + 1];
     if (tid < cg2) {
@@ -683,12 +667,6 @@ __global__ __launch_bounds__(256) void gn_finish_partials_kernel(const float2* _
     }
 }
 
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -711,9 +689,7 @@ int gd_nn_groupnorm_silu_forward(void* stream, const void* x, void* y, const voi
                            g.ppb_stats, eps, stats_ws, mean_rstd, N, 0);
     hipLaunchKernelGGL(gn_apply_kernel, grid, block, 0, s, (const bf16x8*)x, (bf16x8*)y, (const uint16_t*)gamma,
                        (const uint16_t*)beta, HW, C, G, g.vpp, g.rows, g.ppb, apply_silu, mean_rstd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_groupnorm_silu_fused_supported(int N, int HW, int C, int G)
@@ -756,9 +732,7 @@ int gd_nn_groupnorm_silu_fused_backward(void* stream, const void* x, const void*
     else if (total <= 1024 * 8) GD_GN_FUSED_BWD(1024, 8);
     else GD_GN_FUSED_BWD(1024, 16);
 #undef GD_GN_FUSED_BWD
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_groupnorm_silu_fused_forward_stats(void* stream, const void* x, void* y, const void* gamma, const void* beta, int N,
@@ -779,9 +753,7 @@ int gd_nn_groupnorm_silu_fused_forward_stats(void* stream, const void* x, void* 
     else if (total <= 1024 * 16) GD_GN_FUSED(1024, 16);
     else GD_GN_FUSED(1024, 32);      // (1024 x 64 = the 640 / 960-channel 64x64 maps would need 24 spilled registers)
 #undef GD_GN_FUSED
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_groupnorm_silu_forward_fp8(void* stream, const void* x, void* y_fp8, const void* gamma, const void* beta, int N,
@@ -797,9 +769,7 @@ int gd_nn_groupnorm_silu_forward_fp8(void* stream, const void* x, void* y_fp8, c
                        g.ppb_stats, eps, stats_ws, mean_rstd, N, 0);
     hipLaunchKernelGGL(gn_apply_fp8_kernel, grid, block, 0, s, (const bf16x8*)x, (uint2*)y_fp8, (const uint16_t*)gamma,
                        (const uint16_t*)beta, HW, C, G, g.vpp, g.rows, g.ppb, apply_silu, mean_rstd, inv_scale);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_groupnorm_stats(void* stream, const void* x, int N, int HW, int C, int G, float eps, double* stats_ws,
@@ -812,9 +782,7 @@ int gd_nn_groupnorm_stats(void* stream, const void* x, int N, int HW, int C, int
     dim3 block(g.threads), grid_s(g.nchunks_stats, N);
     hipLaunchKernelGGL(gn_stats_kernel, grid_s, block, g.lds, s, (const bf16x8*)x, HW, C, G, g.vpp, g.rows,
                        g.ppb_stats, eps, stats_ws, mean_rstd, N, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_groupnorm_finish_partials(void* stream, const float* stat_part, int N, size_t rows, int C, int G, int HW,
@@ -825,9 +793,7 @@ int gd_nn_groupnorm_finish_partials(void* stream, const float* stat_part, int N,
         return fail(GD_NN_ERR_INVALID_ARG, "finish_partials: need C % G == 0 and (C / G) % 4 == 0");
     hipLaunchKernelGGL(gn_finish_partials_kernel, dim3(G, N), dim3(256), 0, (hipStream_t)stream,
                        (const float2*)stat_part, (int)rows, C, G, (double)HW * (double)(C / G), eps, mean_rstd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_groupnorm_silu_backward(void* stream, const void* x, const void* dy, const void* gamma, const void* beta,
@@ -850,9 +816,7 @@ int gd_nn_groupnorm_silu_backward(void* stream, const void* x, const void* dy, c
     hipLaunchKernelGGL(gn_bwd_apply_kernel, grid, block, 0, s, (const bf16x8*)x, (const bf16x8*)dy,
                        (const uint16_t*)gamma, (const uint16_t*)beta, mean_rstd, (bf16x8*)dx, HW, C, G, g.vpp, g.rows,
                        g.ppb, apply_silu, m12, (const bf16x8*)add, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 const char* gd_nn_last_error(void) { return g_err; }

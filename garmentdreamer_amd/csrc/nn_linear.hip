@@ -23,14 +23,13 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 #include "nn_math.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+using namespace gdnn;
 
 constexpr int kK = 320, kN = 320, kBM = 32, kWaves = kN / 32, kThreads = 64 * kWaves;
 constexpr int kChunks = kK / 8;                    // 16-byte chunks per row of x (40)
@@ -41,19 +40,7 @@ constexpr int kOutPitch = 656;                     // result tile row pitch (16-
 constexpr int kOutOff = kStages * kStage;
 constexpr int kOutTile = kBM * kOutPitch;           // 20992 B, two of them (the stores of a tile overlap the next one's MFMAs)
 constexpr int kLds = kOutOff + 2 * kOutTile;        // 140288 B
-constexpr uint32_t kOOB = 0x80000000u;
 
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi)
-{
-    f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ void bload_lds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, char* lds_wave_base)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff,
-                                             0, 0);
-}
 
 // GEGLU = true: weight is diffusers' GEGLU projection [2 * 160 nb][320] (hidden rows, then gate rows) and y[M][160 nb] =
 // hidden * gelu(gate): a workgroup owns 160 output channels -- waves 0..4 their hidden rows, waves 5..9 their gate rows --
@@ -79,8 +66,7 @@ __global__ __launch_bounds__(kThreads) void linear_320_kernel(const uint16_t* __
     const int tiles_per_pass = (int)(gridDim.x / nb);
     constexpr int kOutCh = GEGLU ? kN / 2 : kN;            // output channels of a workgroup
     const int ldy = kOutCh * nb;
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)y, 0, (int)(uint32_t)((size_t)M * (size_t)ldy * 2u), 0x00020000);      // < 4 GiB (gd_nn_linear_320_supported)
+    const __amdgpu_buffer_rsrc_t rs_y = buffer_rsrc(y, (uint32_t)((size_t)M * (size_t)ldy * 2u));   // < 4 GiB (gd_nn_linear_320_supported)
     // first of this wave's 32 weight rows
     const int wrow = GEGLU ? (wave < kWaves / 2 ? kOutCh * cb + 32 * wave : kOutCh * nb + kOutCh * cb + 32 * (wave - kWaves / 2))
                            : kN * cb + 32 * wave;
@@ -94,8 +80,7 @@ __global__ __launch_bounds__(kThreads) void linear_320_kernel(const uint16_t* __
 #pragma unroll
     for (int q = 0; q < 4; q++) bq2[q] = bias ? *(const uint2*)(bias + wrow + 8 * q + 4 * fk) : make_uint2(0u, 0u);
 
-    const __amdgpu_buffer_rsrc_t rs_x =
-        __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)((uint32_t)M * (uint32_t)(kK * 2)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(x, (uint32_t)M * (uint32_t)(kK * 2));
     // DMA pieces of one stage: 32 rows x 48 slots = 24 pieces of 64 lanes: waves 0..7 issue kDma = 3 each per tile
     // (pieces w, w + 8, w + 16), waves 8 and 9 none -- the s_waitcnt immediates below count instructions per wave.
     constexpr int kPieces = kBM * kSlots / 64, kDmaWaves = 8, kDma = kPieces / kDmaWaves;
@@ -221,12 +206,6 @@ __global__ __launch_bounds__(kThreads) void linear_320_kernel(const uint16_t* __
     }
 }
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
 
 template <bool GEGLU>
 int launch_k320(void* stream, const void* x, const void* weight, const void* bias, void* y, int64_t M, int nb)
@@ -246,9 +225,7 @@ int launch_k320(void* stream, const void* x, const void* weight, const void* bia
     while (grid > 8 * nb && (grid / nb) / 2 >= ntiles) grid /= 2;
     hipLaunchKernelGGL(linear_320_kernel<GEGLU>, dim3(grid), dim3(kThreads), kLds, (hipStream_t)stream, (const uint16_t*)x,
                        (const uint16_t*)weight, (const uint16_t*)bias, (uint16_t*)y, (int)M, ntiles, nb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 }  // namespace

@@ -26,26 +26,12 @@
 #include <string.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 
 namespace {
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-struct alignas(16) u32x4 { uint32_t w[4]; };
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi)
-{
-    f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float lo16(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi16(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+using namespace gdnn;
 
 // rows per partial sum of the weight-gradient reduction: 32, or M / 64 for long token sequences (at most 64 chunks: the
 // fixed-order second stage is a serial loop over them)
@@ -445,9 +431,7 @@ int gd_nn_lora_colreduce_group_launch(void* stream, const void* table_host, int 
             else
                 hipLaunchKernelGGL(lora_colreduce_group_finish_kernel, dim3(grid2_x, n), dim3(256), 0, (hipStream_t)stream, a);
         }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 const char* gd_nn_lora_last_error(void) { return g_err; }
@@ -461,9 +445,7 @@ int gd_nn_lora_rowdot(void* stream, const void* a, const float* w, float* h, int
         hipLaunchKernelGGL(lora_rowdot_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)a, w, (float4*)h, (int)M, K / 8, scale);
     else
         hipLaunchKernelGGL(lora_rowdot_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)a, w, (float4*)h, (int)M, K / 8, scale);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_lora_rank4_add(void* stream, const float* h, const float* w, const void* base, void* y, int64_t M, int N, int w_is_n_by_4)
@@ -477,9 +459,7 @@ int gd_nn_lora_rank4_add(void* stream, const float* h, const float* w, const voi
         hipLaunchKernelGGL(lora_rank4_add_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)h, w, (const u32x4*)base, (u32x4*)y, nvec, N / 8);
     else
         hipLaunchKernelGGL(lora_rank4_add_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)h, w, (const u32x4*)base, (u32x4*)y, nvec, N / 8);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_lora_row_fused(void* stream, const void* a, const float* w1, const float* w2, const void* base, float* h, void* y,
@@ -495,9 +475,7 @@ int gd_nn_lora_row_fused(void* stream, const void* a, const float* w1, const flo
     else
         hipLaunchKernelGGL(lora_row_fused_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const u32x4*)a, w1, w2,
                            (const u32x4*)base, (float4*)h, (u32x4*)y, (int)M, K / 8, N / 8, scale);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 size_t gd_nn_lora_colreduce_scratch_floats(int64_t M, int J)
@@ -519,9 +497,7 @@ int gd_nn_lora_colreduce(void* stream, const void* a, const float* v, float* scr
                        (const float4*)v, scratch, (int)M, J8, rows);
     hipLaunchKernelGGL(lora_colreduce_finish_kernel, dim3((4 * J + 255) / 256), dim3(256), 0, (hipStream_t)stream, scratch, g, chunks, J,
                        scale, g_is_j_by_4);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 size_t gd_nn_lora_colreduce_pair_scratch_floats(int64_t M, int N, int K)
@@ -550,9 +526,7 @@ int gd_nn_lora_colreduce_pair_into(void* stream, const void* dy, const float* hs
     const int jmax = N > K ? N / 8 : K / 8;
     hipLaunchKernelGGL(lora_colreduce_pair_kernel, dim3((jmax + 63) / 64, chunks, 2), dim3(256), 0, (hipStream_t)stream, p, (int)M, rows);
     hipLaunchKernelGGL(lora_colreduce_pair_finish_kernel, dim3((4 * (N + K) + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, chunks);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -1,17 +1,10 @@
-// Packed-fp32 helpers shared by the row passes (nn_elementwise.hip) and the GEMM epilogues that fuse them (nn_linear.hip):
-// one definition, so that a fused epilogue rounds exactly like the separate kernel it replaces.
+// Packed-fp32 math shared by the row passes (nn_elementwise.hip) and the GEMM epilogues that fuse them (nn_linear.hip,
+// nn_gemm.hip): one definition, so that a fused epilogue rounds exactly like the separate kernel it replaces.  The
+// packing and rounding primitives underneath are nn_device.h's.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "nn_device.h"
 
 namespace gdnn {
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f2 unpack2(uint32_t w) { return f2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; }
-__device__ __forceinline__ uint32_t pack2(f2 v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2_t)); }
-__device__ __forceinline__ f2 round_bf16(f2 v) { return unpack2(pack2(v)); }
 
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, three orders below a bf16 ulp of the GELU): one rcp, one
 // exp and a degree-5 Horner instead of libm erff's ~40 instructions -- the kernels are VALU-bound on this function.

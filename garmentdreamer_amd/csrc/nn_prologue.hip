@@ -22,24 +22,12 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 
 namespace {
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-__device__ __forceinline__ uint16_t f2bf(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
+using namespace gdnn;
 
 // source coordinate of output index o (PyTorch area_pixel_compute_source_index, align_corners = False, bilinear)
 __device__ __forceinline__ void src_index(int o, float scale, int in_size, int& i0, int& i1, float& w1)
@@ -172,7 +160,7 @@ int gd_nn_vae_prologue_forward(void* stream, const float* x, void* y, int N, int
     const int64_t total = (int64_t)N * OH * OW;
     hipLaunchKernelGGL(vae_prologue_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        x, (uint16_t*)y, N, H, W, OH, OW, (float)H / (float)OH, (float)W / (float)OW);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "vae_prologue: launch failed");
+    return launch_status("vae_prologue: launch failed");
 }
 
 int gd_nn_vae_prologue_backward(void* stream, const void* dy, float* dx, int N, int H, int W, int OH, int OW, int CG)
@@ -183,7 +171,7 @@ int gd_nn_vae_prologue_backward(void* stream, const void* dy, float* dx, int N, 
     const int64_t total = (int64_t)N * H * W;
     hipLaunchKernelGGL(vae_prologue_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)dy, dx, N, H, W, OH, OW, CG, (float)H / (float)OH, (float)W / (float)OW);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "vae_prologue backward: launch failed");
+    return launch_status("vae_prologue backward: launch failed");
 }
 
 int gd_nn_sparsity_forward(void* stream, const float* depth, const float* dmax, int64_t n, double* sums2)
@@ -194,7 +182,7 @@ int gd_nn_sparsity_forward(void* stream, const float* depth, const float* dmax, 
     const int64_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(sparsity_fwd_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0,
                        (hipStream_t)stream, depth, dmax, n, sums2);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "sparsity: launch failed");
+    return launch_status("sparsity: launch failed");
 }
 
 int gd_nn_sparsity_backward(void* stream, const float* depth, const float* dmax, const float* grad_out, int64_t n,
@@ -204,7 +192,7 @@ int gd_nn_sparsity_backward(void* stream, const float* depth, const float* dmax,
     const int64_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(sparsity_bwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                        (hipStream_t)stream, depth, dmax, grad_out, n, d_depth);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "sparsity backward: launch failed");
+    return launch_status("sparsity backward: launch failed");
 }
 
 }  // extern "C"

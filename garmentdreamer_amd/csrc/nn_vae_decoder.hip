@@ -23,30 +23,13 @@
 #include <stdio.h>
 
 #include "../../include/gd_nn.h"
+#include "nn_device.h"
+#include "nn_host.h"
 #include "nn_math.h"
 
 namespace {
 
-thread_local char g_err[256] = "";
-int fail(int code, const char* msg)
-{
-    snprintf(g_err, sizeof(g_err), "%s", msg);
-    return code;
-}
-
-using gdnn::bf2_t;
-using gdnn::f2;
-using gdnn::pack2;
-using gdnn::unpack2;
-
-__device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f)
-{
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
+using namespace gdnn;
 
 template <bool BF16_IN> __device__ __forceinline__ float load_in(const void* p, int64_t i)
 {
@@ -170,8 +153,8 @@ __device__ __forceinline__ void load_slice(const uint16_t* __restrict__ x, uint4
     }
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) u32x4* const_u4_ptr;   // scalar-cache loads (uniform addresses)
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) u32x4_t* const_u4_ptr;   // scalar-cache loads (uniform addresses)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void head_kernel(const uint16_t* __restrict__ x, const float* __restrict__ mean_rstd,
@@ -239,9 +222,9 @@ __global__ __launch_bounds__(256) void head_kernel(const uint16_t* __restrict__ 
             for (int k8 = 0; k8 < HD_SLICE / 8; k8++) {
                 const uint4 a = *(const uint4*)&ap[k8 * 4];
                 const int wi = (c0 + k8 * 8) >> 3;
-                const u32x4 w0 = wc[(0 * 9 + tap) * (C >> 3) + wi];
-                const u32x4 w1 = wc[(1 * 9 + tap) * (C >> 3) + wi];
-                const u32x4 w2 = wc[(2 * 9 + tap) * (C >> 3) + wi];
+                const u32x4_t w0 = wc[(0 * 9 + tap) * (C >> 3) + wi];
+                const u32x4_t w1 = wc[(1 * 9 + tap) * (C >> 3) + wi];
+                const u32x4_t w2 = wc[(2 * 9 + tap) * (C >> 3) + wi];
                 const uint32_t av[4] = {a.x, a.y, a.z, a.w};
                 const uint32_t v0[4] = {w0.x, w0.y, w0.z, w0.w}, v1[4] = {w1.x, w1.y, w1.z, w1.w},
                                v2[4] = {w2.x, w2.y, w2.z, w2.w};
@@ -302,7 +285,7 @@ int gd_nn_vae_decoder_stem(void* stream, const void* latents, int latents_bf16, 
         hipLaunchKernelGGL(stem_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, latents, inv_scale,
                            (const uint16_t*)pq_weight, (const uint16_t*)pq_bias, (const uint16_t*)weight,
                            (const uint16_t*)bias, (uint16_t*)y, h, w, Cout);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "vae_decoder_stem: launch failed");
+    return launch_status("vae_decoder_stem: launch failed");
 }
 
 int gd_nn_vae_decoder_head_supported(int N, int H, int W, int C, int G)
@@ -333,7 +316,7 @@ int gd_nn_vae_decoder_head(void* stream, const void* x, const float* mean_rstd, 
         hipLaunchKernelGGL(head_kernel<GD_NN_VAE_HEAD_IMAGE>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x,
                            mean_rstd, (const uint16_t*)gamma, (const uint16_t*)beta, G, (const uint16_t*)weight,
                            (const uint16_t*)bias, out, H, W, C);
-    return hipGetLastError() == hipSuccess ? 0 : fail(GD_NN_ERR_HIP, "vae_decoder_head: launch failed");
+    return launch_status("vae_decoder_head: launch failed");
 }
 
 const char* gd_nn_vae_decoder_last_error(void) { return g_err; }
