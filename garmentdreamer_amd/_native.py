@@ -94,6 +94,9 @@ SCENE_SIGNATURES = {
                                    C.POINTER(C.c_uint32)]),
     "gd_scene_densify_apply": (_i, [_vp, _i, _i, C.POINTER(C.c_int), _i, _i, _i, C.POINTER(C.c_uint32)] + [_vp] * 8),
     "gd_scene_densify_last_error": (C.c_char_p, []),
+    "gd_scene_shell_grid": (_i, [_PF, _PF, _f, _PF, C.POINTER(_i)]),
+    "gd_scene_shell_scratch_bytes": (C.c_size_t, [_i, C.c_int64]),
+    "gd_scene_shell_search": (_i, [_vp, _i, _vp, _i, _vp, _PF, _PF, _f, _vp, _vp, _vp]),
     "gd_scene_last_error": (C.c_char_p, []),
 }
 

@@ -136,5 +136,6 @@ void launch_render_backward(hipStream_t s, int V, int W, int H, int tiles_x, int
                             float* rows /*[4R][10]: the row of sums of clist entry i at index i*/, const uint4* clist,
                             const uint32_t* strip_count, const uint32_t* tile_perm = nullptr);
 
+int scene_fail(int code, const char* msg);   // records msg for gd_scene_last_error() and returns code (raster_scene.hip)
 
 }  // namespace gd

@@ -343,6 +343,9 @@ KnnScratch carve_knn(char* base, int P)
 }
 
 }  // namespace
+
+int scene_fail(int code, const char* msg) { return sfail(code, msg); }
+
 }  // namespace gd
 
 extern "C" {

@@ -245,6 +245,15 @@ class GaussianModel(GaussianParams):
                     "opacity": opacities, "scaling": scales, "rotation": rots})
         self.max_radii2D = torch.zeros((P,), device=dev)
 
+    def create_from_template(self, mesh_path: str, spatial_lr_scale: float = 4.0, **kw):
+        """``create_from_pcd(pcb(), cameras_extent)`` of the reference's stage 1 (GaussianDreamer.py:165-177, 421-427):
+        the point cloud of ``template.template_point_cloud(mesh_path, **kw)`` (surface samples of the garment template
+        + the shell of nearby candidates, HIP radius search).  Returns ``bound`` (= radius * scale)."""
+        from .template import template_point_cloud
+        points, colors, bound = template_point_cloud(mesh_path, device=self.device, **kw)
+        self.create_from_pcd(points.cpu().numpy(), colors.cpu().numpy(), spatial_lr_scale)
+        return bound
+
     # ---- optimisation (training_setup / update_learning_rate, :149-177) -----------------------
     def training_setup(self, training_args=OptimizationParams):
         a = training_args

@@ -21,7 +21,11 @@
  *                            event as a classification pass and ONE sweep that writes the new flat parameter /
  *                            exp_avg / exp_avg_sq buffers (csrc/raster_densify.hip).
  *
- * Return 0 on success, negative on error (gd_scene_last_error(); gd_scene_densify_last_error() for the last two).
+ *   gd_scene_shell_grid / _search  <- GaussianDreamer.add_points
+ *                            (Garment_3DGS/threestudio/systems/GaussianDreamer.py:115-144): nearest template sample of
+ *                            every candidate point within a fixed radius, on a uniform grid (csrc/raster_template.hip).
+ *
+ * Return 0 on success, negative on error (gd_scene_last_error(); gd_scene_densify_last_error() for the densify pair).
  */
 #ifndef GD_SCENE_H_INCLUDED
 #define GD_SCENE_H_INCLUDED
@@ -101,6 +105,27 @@ int gd_scene_densify_apply(void* stream, int P, int ngroups, const int* width, i
                            const float* exp_avg, const float* exp_avg_sq, float* new_flat, float* new_exp_avg,
                            float* new_exp_avg_sq);
 const char* gd_scene_densify_last_error(void);
+
+/* ---- fixed-radius nearest-sample search (template initialisation) --------------------------------------------------
+ * The grid over the samples' bounding box: cell edge = max(radius, longest extent / GD_SCENE_SHELL_AXIS_CELLS), so an
+ * axis never has more than GD_SCENE_SHELL_AXIS_CELLS + 1 = 256 cells and the grid never more than 2^24;
+ * dims[k] = floor(extent[k] / edge) + 1 >= 1.  The edge is never below the radius, so a query's neighbourhood is its
+ * own cell and the cells next to it.  Host arithmetic only (bbox_min / bbox_max: HOST float[3]); -1 for a radius that
+ * is not positive and finite or a box that is not finite with max >= min. */
+#define GD_SCENE_SHELL_AXIS_CELLS 255
+int gd_scene_shell_grid(const float* bbox_min, const float* bbox_max, float radius, float* cell_edge, int* dims);
+
+/* bytes of device scratch the search needs for S samples on a grid of `cells` = dims[0] * dims[1] * dims[2] cells */
+size_t gd_scene_shell_scratch_bytes(int S, int64_t cells);
+
+/* samples: float [S][3], queries: float [Q][3] (device); bbox_min / bbox_max: HOST float[3], a box that contains every
+ * sample (the grid is planned from it as above); nearest: int32 [Q] out, dist2: float [Q] out.
+ *   d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)) in fp32; the smallest d2 over the cells around the query wins, on
+ *   equal d2 the lowest sample index; nearest[q] = that index if d2 < fl(radius radius), else -1; dist2[q] = the
+ *   smallest d2 seen (+inf if the visited cells were empty; for a rejected query it covers the visited cells only).
+ * A query outside the box is legal (it finds fewer cells).  Reruns are bit-identical.  No host synchronisation. */
+int gd_scene_shell_search(void* stream, int S, const float* samples, int Q, const float* queries, const float* bbox_min,
+                          const float* bbox_max, float radius, int* nearest, float* dist2, void* scratch);
 
 const char* gd_scene_last_error(void);
 
