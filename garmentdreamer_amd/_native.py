@@ -99,6 +99,17 @@ SCENE_SIGNATURES = {
     "gd_scene_shell_search": (_i, [_vp, _i, _vp, _i, _vp, _PF, _PF, _f, _vp, _vp, _vp]),
     "gd_scene_last_error": (C.c_char_p, []),
 }
+# mesh render path of the NeTF stage in the same library (include/gd_mesh.h)
+MESH_SIGNATURES = {
+    "gd_mesh_rasterize_scratch_bytes": (C.c_size_t, [_i] * 3),
+    "gd_mesh_rasterize": (_i, [_vp] + [_i] * 4 + [_vp] * 4),                       # stream, V F H W, pos tri rast scratch
+    "gd_mesh_interpolate_forward": (_i, [_vp] + [_i] * 5 + [_vp] * 4),             # stream, V F C H W, attr rast tri out
+    "gd_mesh_interpolate_backward_scratch_bytes": (C.c_size_t, [_i] * 2),
+    "gd_mesh_interpolate_backward": (_i, [_vp] + [_i] * 5 + [_vp] * 8),            # ..., pos tri rast dout ptr idx dattr scratch
+    "gd_mesh_antialias_weights": (_i, [_vp] + [_i] * 4 + [_vp] * 5),               # stream, V F H W, rast pos tri opp wts
+    "gd_mesh_antialias_apply": (_i, [_vp] + [_i] * 3 + [_vp] * 3 + [_i]),          # stream, C H W, in wts out, adjoint
+    "gd_mesh_last_error": (C.c_char_p, []),
+}
 
 
 class NativeLibraryError(RuntimeError):
@@ -126,7 +137,7 @@ def lib():
             L = C.CDLL(_LIB_PATH)
         except OSError as e:  # e.g. libamdhip64 missing
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

@@ -14,6 +14,8 @@ HSA runtime has opened /dev/kfd; otherwise ``graph_replay_safe()`` is False and 
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 
 FLAG = "DEBUG_CLR_GRAPH_PACKET_CAPTURE"
@@ -54,3 +56,20 @@ def configure() -> bool:
 
 def graph_replay_safe() -> bool:
     return configure()
+
+
+@contextlib.contextmanager
+def capture_guard():
+    """Around a hipGraph capture (``torch.cuda.graph`` / ``make_graphed_callables``): collect Python's cyclic garbage
+    BEFORE the capture and keep the cyclic collector off during it.  torch no longer collects on entering a capture, and
+    a collection that happens to run while a stream is capturing may free what a dead cycle still holds -- other
+    CUDAGraphs with their memory pools, streams, events -- from inside the capture; the HIP runtime aborts on that.
+    When a collection runs depends on allocation counts only, so any unrelated change can move it into a capture."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()

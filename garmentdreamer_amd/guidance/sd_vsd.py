@@ -220,7 +220,7 @@ class StableDiffusionVSD(nn.Module):
                 # ... and its own CAPTURE stream: the library GEMMs' workspace (stream-K partial tiles) is keyed by the stream the
                 # call was captured on, so two graphs captured on torch's default capture stream would share one
                 cap = self._capture_stream(dev)
-                with torch.cuda.graph(g, stream=cap), torch.no_grad():
+                with _runtime_env.capture_guard(), torch.cuda.graph(g, stream=cap), torch.no_grad():
                     out = fn(*static)
             entry = self._graphs[key] = (g, static, out, cap)
         g, static, out = entry[:3]
@@ -253,7 +253,7 @@ class StableDiffusionVSD(nn.Module):
             prev_cap = torch.cuda.graph.default_capture_stream
             torch.cuda.graph.default_capture_stream = cap
             try:
-                with nn_ops.workspace_tag(key):
+                with nn_ops.workspace_tag(key), _runtime_env.capture_guard():
                     fn = self._graphs[key] = torch.cuda.make_graphed_callables(module, sample, allow_unused_input=True)
             finally:
                 torch.cuda.graph.default_capture_stream = prev_cap

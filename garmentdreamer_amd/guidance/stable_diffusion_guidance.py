@@ -196,7 +196,7 @@ class StableDiffusionGuidance(nn.Module):
                     self.unet(sx, st, encoder_hidden_states=sc)
             torch.cuda.current_stream(x.device).wait_stream(side)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), torch.no_grad():
+            with _runtime_env.capture_guard(), torch.cuda.graph(g), torch.no_grad():
                 out = self.unet(sx, st, encoder_hidden_states=sc)
             entry = self._unet_graphs[key] = (g, sx, st, sc, out)
         g, sx, st, sc, out = entry
@@ -219,7 +219,8 @@ class StableDiffusionGuidance(nn.Module):
                     return vae.quant_conv(vae.encoder(x))
 
             sample = torch.rand(imgs.shape, device=imgs.device, dtype=imgs.dtype, requires_grad=True)
-            fn = self._vae_graphs[key] = torch.cuda.make_graphed_callables(_Moments(), (sample,))
+            with _runtime_env.capture_guard():
+                fn = self._vae_graphs[key] = torch.cuda.make_graphed_callables(_Moments(), (sample,))
         return fn(imgs)
 
     def encode_images(self, imgs, vae_noise: Optional[torch.Tensor] = None):
