@@ -112,6 +112,17 @@ MESH_SIGNATURES = {
 }
 
 
+# its moving-geometry side: gradients to vertex positions and the visible-vertex mask (include/gd_mesh_deform.h)
+MESH_DEFORM_SIGNATURES = {
+    "gd_mesh_interpolate_backward_rast": (_i, [_vp] + [_i] * 5 + [_vp] * 5),       # stream, V F C H W, attr rast tri dout drast
+    "gd_mesh_rasterize_backward_scratch_bytes": (C.c_size_t, [_i]),
+    "gd_mesh_rasterize_backward": (_i, [_vp] + [_i] * 4 + [_vp] * 8),              # ..., pos tri rast drast ptr idx dpos scratch
+    "gd_mesh_antialias_backward_pos_scratch_bytes": (C.c_size_t, [_i]),
+    "gd_mesh_antialias_backward_pos": (_i, [_vp] + [_i] * 5 + [_vp] * 10),         # stream, V F C H W, rast pos tri opp in dout ptr idx dpos scratch
+    "gd_mesh_visible_vertices": (_i, [_vp] + [_i] * 3 + [_vp] * 3),                # stream, V F npix, rast tri vis
+}
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -137,7 +148,8 @@ def lib():
             L = C.CDLL(_LIB_PATH)
         except OSError as e:  # e.g. libamdhip64 missing
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
+                + list(MESH_DEFORM_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

@@ -17,12 +17,16 @@
 // shuffle tree) writes a [F][3][C] slab, vertex_sum adds each vertex's corners in CSR order.  No atomics.
 // antialias is a gather: aa_weights analyses each pixel's four pairs once per (rast, pos); aa_apply blends any image
 // with those weights, or applies the adjoint.
+// Gradients to vertex positions (include/gd_mesh_deform.h, for the mesh deformer): raster_backward and aa_backward_pos
+// have the shape of corner_grad, a [F][3][4] slab of (x, y, 0, w) per corner that vertex_sum adds per vertex;
+// aa_backward_pos takes each pair's decisions from pair_analyse, the device function aa_weights uses.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/gd_mesh.h"
+#include "../../include/gd_mesh_deform.h"
 
 namespace gd {
 namespace {
@@ -307,29 +311,41 @@ __global__ __launch_bounds__(256) void vertex_sum_kernel(int V, int F, int C, co
 
 __device__ __forceinline__ int sign64(int64_t x) { return (x > 0) - (x < 0); }
 
-// weight pixel p = (r, c) receives from its neighbour n = (rn, cn); horizontal: the pair lies in one row
-__device__ __forceinline__ float pair_weight(int V, int F, int H, int W, const float4* __restrict__ rast,
+// what the analysis of one pair decided (edge < 0: no silhouette edge with t <= 1, no weight)
+struct PairInfo {
+    int t;             // the chosen triangle
+    int edge;          // its deciding edge, running from corner edge + 1 to corner edge + 2
+    bool p_is_inner;   // p is the chosen triangle's pixel I
+    float tt;          // crossing distance from I's centre, from the snapped vertices
+};
+
+// the pair of pixel p = (r, c) and its neighbour n = (rn, cn); horizontal: the pair lies in one row.  The one place the
+// pair's decisions are taken: aa_weights_kernel and aa_backward_pos_kernel both read them here.
+__device__ __forceinline__ bool pair_analyse(int V, int F, int H, int W, const float4* __restrict__ rast,
                                              const float* __restrict__ pos, const int* __restrict__ tri,
                                              const int* __restrict__ opp, int r, int c, int rn, int cn, bool horizontal,
-                                             const float4& rp)
+                                             const float4& rp, PairInfo& o)
 {
+    o.edge = -1;
     const float4 rq = rast[(size_t)rn * W + cn];
     const int idp = (int)rp.w, idn = (int)rq.w;
-    if (idp == idn) return 0.0f;
+    if (idp == idn) return false;
     bool p_is_inner;
     if (idp == 0) p_is_inner = false;
     else if (idn == 0) p_is_inner = true;
     else if (rp.z != rq.z) p_is_inner = rp.z < rq.z;
     else p_is_inner = idp < idn;
     const int t = (p_is_inner ? idp : idn) - 1;
-    if ((unsigned)t >= (unsigned)F) return 0.0f;
+    if ((unsigned)t >= (unsigned)F) return false;
+    o.t = t;
+    o.p_is_inner = p_is_inner;
     const int ri = p_is_inner ? r : rn, ci = p_is_inner ? c : cn;
     int vi[3];
     Vert vv[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         vi[i] = tri[3 * (size_t)t + i];
-        if ((unsigned)vi[i] >= (unsigned)V || !snap_vertex(pos, vi[i], H, W, vv[i])) return 0.0f;
+        if ((unsigned)vi[i] >= (unsigned)V || !snap_vertex(pos, vi[i], H, W, vv[i])) return false;
     }
     // the line through the two centres, in sub-pixel units: y = L for a horizontal pair, x = L for a vertical one
     const int L = horizontal ? 256 * r + 128 : 256 * c + 128;
@@ -360,10 +376,23 @@ __device__ __forceinline__ float pair_weight(int V, int F, int H, int W, const f
         const float x = sa_al + (sb_al - sa_al) * ((line - sa_on) / (sb_on - sa_on));
         const float tt = fabsf(x - centre);
         if (!(tt <= 1.0f)) continue;
-        if (tt > 0.5f) return p_is_inner ? 0.0f : tt - 0.5f;
-        return p_is_inner ? 0.5f - tt : 0.0f;
+        o.edge = i;
+        o.tt = tt;
+        return true;
     }
-    return 0.0f;
+    return false;
+}
+
+// weight pixel p = (r, c) receives from its neighbour n = (rn, cn)
+__device__ __forceinline__ float pair_weight(int V, int F, int H, int W, const float4* __restrict__ rast,
+                                             const float* __restrict__ pos, const int* __restrict__ tri,
+                                             const int* __restrict__ opp, int r, int c, int rn, int cn, bool horizontal,
+                                             const float4& rp)
+{
+    PairInfo o;
+    if (!pair_analyse(V, F, H, W, rast, pos, tri, opp, r, c, rn, cn, horizontal, rp, o)) return 0.0f;
+    if (o.tt > 0.5f) return o.p_is_inner ? 0.0f : o.tt - 0.5f;
+    return o.p_is_inner ? 0.5f - o.tt : 0.0f;
 }
 
 __global__ __launch_bounds__(256) void aa_weights_kernel(int V, int F, int H, int W, const float4* __restrict__ rast,
@@ -411,6 +440,202 @@ __global__ __launch_bounds__(256) void aa_apply_kernel(int C, int H, int W, cons
         }
     }
     out[e] = acc;
+}
+
+// ---- gradients to vertex positions (include/gd_mesh_deform.h; definitions: include/gd_mesh.h) --------------------------
+// The forward's discrete decisions are held fixed and the snapping is removed: the derivatives are those of the
+// continuous functions of the fp32 clip positions.  Both position gradients keep the shape of corner_grad + vertex_sum:
+// one wave per triangle walks the triangle's pixel box, keeps the pixels whose rast id is this triangle, reduces nine
+// values (x, y, w of three corners) with the fixed shuffle tree into a [F][3][4] slab; vertex_sum adds it per vertex.
+
+// drast[p] = (sum_k dout_k (a0_k - a2_k), sum_k dout_k (a1_k - a2_k), 0, 0); zeros on background
+__global__ __launch_bounds__(256) void interp_backward_rast_kernel(int V, int F, int C, int npix,
+                                                                   const float* __restrict__ attr,
+                                                                   const float4* __restrict__ rast,
+                                                                   const int* __restrict__ tri,
+                                                                   const float* __restrict__ dout,
+                                                                   float4* __restrict__ drast)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const int t = (int)rast[p].w - 1;
+    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (t >= 0 && t < F) {
+        const int i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
+        if ((unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V) {
+            for (int k = 0; k < C; k++) {
+                const float d = dout[(size_t)p * C + k], a2 = attr[(size_t)i2 * C + k];
+                o.x += d * (attr[(size_t)i0 * C + k] - a2);
+                o.y += d * (attr[(size_t)i1 * C + k] - a2);
+            }
+        }
+    }
+    drast[p] = o;
+}
+
+// lane-local sums of one wave -> slab[t][i] = (x, y, 0, w), the same tree as corner_grad_kernel
+__device__ __forceinline__ void store_corner_slab(float g[3][3], int t, int lane, float4* __restrict__ slab)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            float x = g[i][j];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+            g[i][j] = x;
+        }
+        if (lane == 0) slab[(size_t)t * 3 + i] = make_float4(g[i][0], g[i][1], 0.0f, g[i][2]);
+    }
+}
+
+__global__ __launch_bounds__(256) void raster_backward_kernel(int V, int F, int H, int W, const float* __restrict__ pos,
+                                                              const int* __restrict__ tri,
+                                                              const float4* __restrict__ rast,
+                                                              const float4* __restrict__ drast, float4* __restrict__ slab)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= F) return;
+    float g[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) g[i][j] = 0.0f;
+    TriSetup s;
+    if (setup_triangle(pos, tri, t, V, H, W, s) && s.c0 <= s.c1 && s.r0 <= s.r1) {
+        float4 P[3];   // the indices are in range: setup_triangle checked them
+#pragma unroll
+        for (int i = 0; i < 3; i++) P[i] = reinterpret_cast<const float4*>(pos)[tri[3 * (size_t)t + i]];
+        const int bw = s.c1 - s.c0 + 1, bh = s.r1 - s.r0 + 1;
+        const int64_t npix = (int64_t)bw * bh;
+        const float id = (float)(t + 1);
+        for (int64_t q = lane; q < npix; q += 64) {
+            const int r = s.r0 + (int)(q / bw), c = s.c0 + (int)(q % bw);
+            const size_t p = (size_t)r * W + c;
+            if (rast[p].w != id) continue;
+            const float4 d = drast[p];
+            const float fx = (float)(2 * c + 1) / (float)W - 1.0f, fy = (float)(2 * r + 1) / (float)H - 1.0f;
+            float qx[3], qy[3];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                qx[i] = P[i].x - fx * P[i].w;
+                qy[i] = P[i].y - fy * P[i].w;
+            }
+            const float a0 = qx[1] * qy[2] - qy[1] * qx[2];
+            const float a1 = qx[2] * qy[0] - qy[2] * qx[0];
+            const float a2 = qx[0] * qy[1] - qy[0] * qx[1];
+            const float S = (a0 + a1) + a2;
+            if (S == 0.0f || !finite_f(S)) continue;
+            const float u = a0 / S, v = a1 / S;
+            const float m = d.x * u + d.y * v;
+            const float g0 = (d.x - m) / S, g1 = (d.y - m) / S, g2 = -m / S;   // dL/da_i
+            const float dqx[3] = {g2 * qy[1] - g1 * qy[2], g0 * qy[2] - g2 * qy[0], g1 * qy[0] - g0 * qy[1]};
+            const float dqy[3] = {g1 * qx[2] - g2 * qx[1], g2 * qx[0] - g0 * qx[2], g0 * qx[1] - g1 * qx[0]};
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                g[i][0] += dqx[i];
+                g[i][1] += dqy[i];
+                g[i][2] += -(fx * dqx[i]) - fy * dqy[i];
+            }
+        }
+    }
+    store_corner_slab(g, t, lane, slab);
+}
+
+__global__ __launch_bounds__(256) void aa_backward_pos_kernel(int V, int F, int C, int H, int W,
+                                                              const float4* __restrict__ rast,
+                                                              const float* __restrict__ pos, const int* __restrict__ tri,
+                                                              const int* __restrict__ opp, const float* __restrict__ in,
+                                                              const float* __restrict__ dout, float4* __restrict__ slab)
+{
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= F) return;
+    float g[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) g[i][j] = 0.0f;
+    TriSetup s;
+    if (setup_triangle(pos, tri, t, V, H, W, s) && s.c0 <= s.c1 && s.r0 <= s.r1) {
+        float4 P[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) P[i] = reinterpret_cast<const float4*>(pos)[tri[3 * (size_t)t + i]];
+        const int bw = s.c1 - s.c0 + 1, bh = s.r1 - s.r0 + 1;
+        const int64_t npix = (int64_t)bw * bh;
+        const float id = (float)(t + 1);
+        const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;
+        for (int64_t q = lane; q < npix; q += 64) {
+            const int r = s.r0 + (int)(q / bw), c = s.c0 + (int)(q % bw);
+            const size_t p = (size_t)r * W + c;
+            const float4 rp = rast[p];
+            if (rp.w != id) continue;
+            // the pixel's four pairs in the order of wts; a pair counts here only if this pixel is its I
+            for (int k = 0; k < 4; k++) {
+                const bool horizontal = k < 2;
+                const int rn = r + (k == 2 ? -1 : k == 3 ? 1 : 0), cn = c + (k == 0 ? -1 : k == 1 ? 1 : 0);
+                if (rn < 0 || rn >= H || cn < 0 || cn >= W) continue;
+                PairInfo o;
+                if (!pair_analyse(V, F, H, W, rast, pos, tri, opp, r, c, rn, cn, horizontal, rp, o) || !o.p_is_inner)
+                    continue;
+                const size_t n = (size_t)rn * W + cn;
+                const bool onto_outer = o.tt > 0.5f;
+                float dw = 0.0f;
+                if (onto_outer)
+                    for (int ch = 0; ch < C; ch++) dw += dout[n * C + ch] * (in[p * C + ch] - in[n * C + ch]);
+                else
+                    for (int ch = 0; ch < C; ch++) dw += dout[p * C + ch] * (in[n * C + ch] - in[p * C + ch]);
+                const float dt = onto_outer ? dw : -dw;
+                const int e = o.edge;
+                const float4 pa = e == 0 ? P[1] : e == 1 ? P[2] : P[0];
+                const float4 pb = e == 0 ? P[2] : e == 1 ? P[0] : P[1];
+                const float sxa = (pa.x / pa.w * 0.5f + 0.5f) * (float)W, sya = (pa.y / pa.w * 0.5f + 0.5f) * (float)H;
+                const float sxb = (pb.x / pb.w * 0.5f + 0.5f) * (float)W, syb = (pb.y / pb.w * 0.5f + 0.5f) * (float)H;
+                const float al_a = horizontal ? sxa : sya, on_a = horizontal ? sya : sxa;
+                const float al_b = horizontal ? sxb : syb, on_b = horizontal ? syb : sxb;
+                const float line = (horizontal ? (float)r : (float)c) + 0.5f;
+                const float centre = (horizontal ? (float)c : (float)r) + 0.5f;
+                const float D = on_b - on_a;
+                if (D == 0.0f || !finite_f(D)) continue;
+                const float sp = (line - on_a) / D;
+                const float x = al_a + (al_b - al_a) * sp;
+                const float gx = x > centre ? dt : x < centre ? -dt : 0.0f;     // dL/dx*
+                const float d_al_a = gx * (1.0f - sp), d_al_b = gx * sp;
+                const float ds = gx * (al_b - al_a);
+                const float d_on_a = ds * (sp - 1.0f) / D, d_on_b = -(ds * sp) / D;
+                const float dsxa = horizontal ? d_al_a : d_on_a, dsya = horizontal ? d_on_a : d_al_a;
+                const float dsxb = horizontal ? d_al_b : d_on_b, dsyb = horizontal ? d_on_b : d_al_b;
+                const float ga[3] = {dsxa * hw / pa.w, dsya * hh / pa.w,
+                                     -(dsxa * hw * pa.x + dsya * hh * pa.y) / (pa.w * pa.w)};
+                const float gb[3] = {dsxb * hw / pb.w, dsyb * hh / pb.w,
+                                     -(dsxb * hw * pb.x + dsyb * hh * pb.y) / (pb.w * pb.w)};
+                const int ca = e == 2 ? 0 : e + 1, cb = e == 0 ? 2 : e - 1;      // corners (e + 1) % 3 and (e + 2) % 3
+#pragma unroll
+                for (int i = 0; i < 3; i++)
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        if (i == ca) g[i][j] += ga[j];
+                        if (i == cb) g[i][j] += gb[j];
+                    }
+            }
+        }
+    }
+    store_corner_slab(g, t, lane, slab);
+}
+
+__global__ __launch_bounds__(256) void visible_vertices_kernel(int V, int F, int npix, const float4* __restrict__ rast,
+                                                               const int* __restrict__ tri, uint8_t* __restrict__ vis)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const int t = (int)rast[p].w - 1;
+    if (t < 0 || t >= F) return;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int v = tri[3 * (size_t)t + i];
+        if ((unsigned)v < (unsigned)V) vis[v] = 1;
+    }
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -546,6 +771,82 @@ int gd_mesh_antialias_apply(void* stream, int C, int H, int W, const float* in, 
     hipLaunchKernelGGL(aa_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, H, W, in,
                        (const float4*)wts, out, adjoint);
     return launched("antialias apply");
+}
+
+// ---- include/gd_mesh_deform.h ------------------------------------------------------------------------------------------
+
+int gd_mesh_interpolate_backward_rast(void* stream, int V, int F, int C, int H, int W, const float* attr,
+                                      const float* rast, const int* tri, const float* dout, float* drast)
+{
+    using namespace gd;
+    if (const char* err = check_frame(H, W)) return mfail(-1, err);
+    if (V < 0 || F < 0) return mfail(-1, "interpolate: V and F must be >= 0");
+    if (C < 1 || C > GD_MESH_MAX_CHANNELS) return mfail(-1, "interpolate: C must be in [1, 8]");
+    if (!rast || !dout || !drast || (F > 0 && (!attr || !tri))) return mfail(-1, "interpolate: null pointer");
+    hipLaunchKernelGGL(interp_backward_rast_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, F, C,
+                       H * W, attr, (const float4*)rast, tri, dout, (float4*)drast);
+    return launched("interpolate backward (rast)");
+}
+
+size_t gd_mesh_rasterize_backward_scratch_bytes(int F)
+{
+    if (F < 0) return 0;
+    return gd::align_up((size_t)F * 3 * 4 * sizeof(float));
+}
+
+int gd_mesh_rasterize_backward(void* stream, int V, int F, int H, int W, const float* pos, const int* tri,
+                               const float* rast, const float* drast, const int* corner_ptr, const int* corner_idx,
+                               float* dpos, void* scratch)
+{
+    using namespace gd;
+    if (const char* err = check_frame(H, W)) return mfail(-1, err);
+    if (V < 0 || F < 0) return mfail(-1, "rasterize backward: V and F must be >= 0");
+    if (V == 0) return 0;
+    if (!rast || !drast || !dpos || !corner_ptr || (F > 0 && (!pos || !tri || !corner_idx || !scratch)))
+        return mfail(-1, "rasterize backward: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (F > 0)
+        hipLaunchKernelGGL(raster_backward_kernel, dim3((F + 3) / 4), dim3(256), 0, s, V, F, H, W, pos, tri,
+                           (const float4*)rast, (const float4*)drast, (float4*)scratch);
+    const int64_t n = (int64_t)V * 4;
+    hipLaunchKernelGGL(vertex_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, V, F, 4, corner_ptr,
+                       corner_idx, (const float*)scratch, dpos);
+    return launched("rasterize backward");
+}
+
+size_t gd_mesh_antialias_backward_pos_scratch_bytes(int F) { return gd_mesh_rasterize_backward_scratch_bytes(F); }
+
+int gd_mesh_antialias_backward_pos(void* stream, int V, int F, int C, int H, int W, const float* rast, const float* pos,
+                                   const int* tri, const int* opp, const float* in, const float* dout,
+                                   const int* corner_ptr, const int* corner_idx, float* dpos, void* scratch)
+{
+    using namespace gd;
+    if (const char* err = check_frame(H, W)) return mfail(-1, err);
+    if (V < 0 || F < 0) return mfail(-1, "antialias backward: V and F must be >= 0");
+    if (C < 1 || C > 4096) return mfail(-1, "antialias: C must be in [1, 4096]");
+    if (V == 0) return 0;
+    if (!rast || !in || !dout || !dpos || !corner_ptr || (F > 0 && (!pos || !tri || !opp || !corner_idx || !scratch)))
+        return mfail(-1, "antialias backward: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (F > 0)
+        hipLaunchKernelGGL(aa_backward_pos_kernel, dim3((F + 3) / 4), dim3(256), 0, s, V, F, C, H, W, (const float4*)rast,
+                           pos, tri, opp, in, dout, (float4*)scratch);
+    const int64_t n = (int64_t)V * 4;
+    hipLaunchKernelGGL(vertex_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, V, F, 4, corner_ptr,
+                       corner_idx, (const float*)scratch, dpos);
+    return launched("antialias backward (pos)");
+}
+
+int gd_mesh_visible_vertices(void* stream, int V, int F, int npix, const float* rast, const int* tri, uint8_t* vis)
+{
+    using namespace gd;
+    if (V < 0 || F < 0) return mfail(-1, "visible vertices: V and F must be >= 0");
+    if (npix <= 0 || npix > 8192 * 8192) return mfail(-1, "visible vertices: npix must be in [1, 8192^2]");
+    if (V == 0 || F == 0) return 0;
+    if (!rast || !tri || !vis) return mfail(-1, "visible vertices: null pointer");
+    hipLaunchKernelGGL(visible_vertices_kernel, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, F, npix,
+                       (const float4*)rast, tri, vis);
+    return launched("visible vertices");
 }
 
 const char* gd_mesh_last_error(void) { return gd::g_mesh_err; }

@@ -10,8 +10,9 @@
   * ``MeshRenderer``          ``Renderer.render`` for ``fix_geo: true`` / ``ssaa = 1``
   * ``projection`` / ``perspective``  the reference's camera matrices (numpy)
 
-Two limits, both outside the reference's live configuration: there is no gradient with respect to vertex positions
-(``pos.requires_grad`` raises), and no near-plane clipping (a triangle with a vertex at ``w <= 0`` is dropped).
+Two limits, both outside the reference's live configuration: there is no gradient with respect to vertex positions in
+this module (``pos.requires_grad`` raises; moving geometry is ``mesh_deform``), and no near-plane clipping (a triangle with
+a vertex at ``w <= 0`` is dropped).
 Tensors follow nvdiffrast's shapes with the minibatch axis optional: ``pos`` [V,4] or [1,V,4], ``rast`` [H,W,4] or
 [1,H,W,4], and so on; the output has a batch axis iff the image input had one.
 """

@@ -10,7 +10,8 @@
  *   gd_mesh_antialias_apply          (rast, pos), and the blend / its adjoint for every image that shares them
  *
  * Two limits, both those of the reference's live configuration (fix_geo: true, cameras orbiting outside the mesh):
- *   1. no gradient w.r.t. vertex positions (nvdiffrast's rast_db and the position gradient of antialias);
+ *   1. no gradient w.r.t. vertex positions in the fixed-geometry entries (nvdiffrast's rast_db and the position
+ *      gradient of antialias): those are the entries of gd_mesh_deform.h, defined at the end of this comment;
  *   2. no near-plane clipping: a triangle with a vertex at w <= 0 is DROPPED, not clipped.
  *
  * ---- rasterize: the definition (fp32, one rounding per operation in the stated order; edges in int64) --------------
@@ -27,6 +28,24 @@
  *               -1 <= zw <= 1;  pi = bi rwi;  s = (p0 + p1) + p2;  u = p0 / s,  v = p1 / s.
  * Visibility:   smallest zw wins; equal bits: lowest triangle index.
  * rast[r][c] = (u, v, zw, float(index + 1)); all four 0 where nothing is covered.  F < 2^24.
+ *
+ * ---- gradients to vertex positions: the definition (entries: gd_mesh_deform.h) ---------------------------------------
+ * The forward stays the one above, with snapped vertices and integer edges.  The gradients are those of the same
+ * functions with the snapping removed and every discrete decision of the forward held fixed: the triangle id per pixel,
+ * the chosen triangle, edge and side of each antialias pair, and its t <= 1 and t > 0.5 branches (nvdiffrast does the
+ * same).  pos is the fp32 clip position [V][4]; z never receives a gradient.
+ * rasterize:    pixel (r, c) won by triangle t: fx = (2c + 1)/W - 1, fy = (2r + 1)/H - 1; for its corners
+ *               q_i = (x_i - fx w_i, y_i - fy w_i);  a0 = q1 x q2, a1 = q2 x q0, a2 = q0 x q1 (2-D cross products);
+ *               u = a0 / (a0 + a1 + a2), v = a1 / (a0 + a1 + a2).  dpos is the exact derivative of this (u, v) in
+ *               x, y, w of the three corners, contracted with drast[..., 0:2]; drast[..., 2:4] (z/w, id) is ignored.
+ * interpolate:  drast.u = sum_k dout_k (a0_k - a2_k), drast.v = sum_k dout_k (a1_k - a2_k) with a_i = attr[tri[id][i]];
+ *               channels 2 and 3 and background pixels are 0.
+ * antialias:    every pair whose analysis (below, at gd_mesh_antialias_weights) finds an edge (a, b) of the chosen
+ *               triangle with t <= 1 has the weight w = t - 0.5 onto O (t > 0.5) or w = 0.5 - t onto I (t <= 0.5), and
+ *               dL/dw = sum_k dout[O]_k (in[I]_k - in[O]_k) or sum_k dout[I]_k (in[O]_k - in[I]_k) respectively.
+ *               t = |x* - centre_I| with x* the formula below on the unsnapped sx = (x/w 0.5 + 0.5) W,
+ *               sy = (y/w 0.5 + 0.5) H.  dL/dw is chained through +-1, sign(x* - centre_I) and x* to x, y, w of the
+ *               vertices a and b.  Each pair counts once, from pixel I's side; pairs without such an edge contribute 0.
  *
  * Return 0 on success, negative on error (gd_mesh_last_error()).
  */

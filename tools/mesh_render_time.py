@@ -1,10 +1,12 @@
-"""Time the mesh render path (garmentdreamer_amd/mesh_render.py) on one GPU: each entry point of include/gd_mesh.h on
-its own, one ``MeshRenderer.render`` and its backward, at 512 x 512 on a generated open tube of about 50 000 triangles.
+"""Time the mesh render path (garmentdreamer_amd/mesh_render.py, mesh_deform.py) on one GPU: each entry point of
+include/gd_mesh.h and include/gd_mesh_deform.h on its own, one ``MeshRenderer.render`` and its backward, one
+``GBufferRenderer.render`` and its backward to the vertices, at 512 x 512 on a generated open tube of about 50 000 triangles.
 
     python tools/mesh_render_time.py [--res 512] [--iters 50]
 
 Prints one JSON line.  Times are medians of HIP-event intervals on the current stream, in microseconds; an entry point
-is one to three kernels (rasterize: memsets + small + large + resolve; interpolate backward: corner_grad + vertex_sum)."""
+is one to three kernels (rasterize: memsets + small + large + resolve; interpolate backward: corner_grad + vertex_sum;
+the two position gradients: one wave-per-triangle kernel + vertex_sum)."""
 import argparse
 import json
 import os
@@ -14,6 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from garmentdreamer_amd import mesh_deform as md  # noqa: E402
 from garmentdreamer_amd import mesh_render as mr  # noqa: E402
 
 
@@ -76,6 +79,28 @@ def main():
     img_g = img.clone().requires_grad_(True)
     aa = mr.antialias(img_g, rast, pos, tri, weights=wts)
 
+    # moving geometry: the gradient to rast alone, the rasterize backward alone, the antialias gradient to pos alone
+    rast_leaf = rast.clone().requires_grad_(True)
+    out_r = md.interpolate(v, rast_leaf, tri, pos, topo)
+    pos_leaf = pos.clone().requires_grad_(True)
+    rast_m = md.rasterize(pos_leaf, tri, (h, w), topo)
+    g_rast = torch.rand_like(rast_m)
+    pos_aa = pos.clone().requires_grad_(True)
+    aa_m = md.antialias(img, rast, pos_aa, tri, topo, weights=wts)
+    mask = torch.clamp(rast[..., -1:], 0, 1).contiguous()
+    aa_mask = md.antialias(mask, rast, pos_aa, tri, topo, weights=wts)
+    g_mask = torch.rand_like(aa_mask)
+    gbuf = md.GBufferRenderer()
+    mvp = torch.from_numpy(proj @ np.linalg.inv(pose)).to(dev)
+    verts = v.clone().requires_grad_(True)
+    channels = ["mask", "position", "normal"]
+
+    def gbuffer_backward():
+        verts.grad = None
+        out = gbuf.render([mvp], verts, tri, vn, (h, w), channels, topology=topo)[0]
+        (((out["mask"] - 0.5) ** 2).mean() + ((out["position"] - img) ** 2).mean()
+         + ((out["normal"] - img) ** 2).mean()).backward()
+
     def render_backward():
         net.zero_grad(set_to_none=True)
         ((renderer.render(pose, proj, h, w)["image"] - img) ** 2).mean().backward()
@@ -88,6 +113,14 @@ def main():
         "interpolate_backward_c3_us": median_us(lambda: out.backward(g, retain_graph=True), args.iters),
         "antialias_apply_c3_us": median_us(lambda: mr.antialias(img, rast, pos, tri, weights=wts), args.iters),
         "antialias_adjoint_c3_us": median_us(lambda: aa.backward(g, retain_graph=True), args.iters),
+        "interpolate_backward_rast_c3_us": median_us(lambda: out_r.backward(g, retain_graph=True), args.iters),
+        "rasterize_backward_us": median_us(lambda: rast_m.backward(g_rast, retain_graph=True), args.iters),
+        "antialias_backward_pos_c3_us": median_us(lambda: aa_m.backward(g, retain_graph=True), args.iters),
+        "antialias_backward_pos_c1_us": median_us(lambda: aa_mask.backward(g_mask, retain_graph=True), args.iters),
+        "visible_vertices_us": median_us(lambda: md.visible_vertices(rast, tri, v.shape[0]), args.iters),
+        "gbuffer_render_us": median_us(lambda: gbuf.render([mvp], verts, tri, vn, (h, w), channels, topology=topo),
+                                       args.iters),
+        "gbuffer_render_and_backward_us": median_us(gbuffer_backward, args.iters),
         "render_us": median_us(lambda: renderer.render(pose, proj, h, w), args.iters),
         "render_and_backward_us": median_us(render_backward, args.iters),
     }
