@@ -122,6 +122,18 @@ MESH_DEFORM_SIGNATURES = {
     "gd_mesh_visible_vertices": (_i, [_vp] + [_i] * 3 + [_vp] * 3),                # stream, V F npix, rast tri vis
 }
 
+# the deformer's geometry terms: normals, uniform Laplacian and normal consistency (include/gd_mesh_geometry.h)
+MESH_GEOMETRY_SIGNATURES = {
+    "gd_mesh_normals_forward": (_i, [_vp] + [_i] * 2 + [_vp] * 7),                 # stream, V F, verts tri ptr idx fn vn len
+    "gd_mesh_normals_backward_scratch_bytes": (C.c_size_t, [_i]),
+    "gd_mesh_normals_backward": (_i, [_vp] + [_i] * 2 + [_vp] * 10),               # ..., verts tri ptr idx vn len dvn dfn dverts scratch
+    "gd_mesh_loss_scratch_bytes": (C.c_size_t, [_i]),
+    "gd_mesh_laplacian_forward": (_i, [_vp] + [_i] * 2 + [_vp] * 6),               # stream, V N, verts ptr idx delta loss scratch
+    "gd_mesh_laplacian_backward": (_i, [_vp] + [_i] * 2 + [_vp] * 5),              # stream, V N, ptr idx delta dloss dverts
+    "gd_mesh_normal_consistency_forward": (_i, [_vp] + [_i] * 2 + [_vp] * 4),      # stream, F P, fn face_nbr loss scratch
+    "gd_mesh_normal_consistency_backward": (_i, [_vp] + [_i] * 2 + [_vp] * 4),     # stream, F P, fn face_nbr dloss dfn
+}
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -149,7 +161,7 @@ def lib():
         except OSError as e:  # e.g. libamdhip64 missing
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
-                + list(MESH_DEFORM_SIGNATURES.items()):
+                + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

@@ -137,5 +137,6 @@ void launch_render_backward(hipStream_t s, int V, int W, int H, int tiles_x, int
                             const uint32_t* strip_count, const uint32_t* tile_perm = nullptr);
 
 int scene_fail(int code, const char* msg);   // records msg for gd_scene_last_error() and returns code (raster_scene.hip)
+int mesh_fail(int code, const char* msg);    // the same for gd_mesh_last_error() (raster_mesh.hip)
 
 }  // namespace gd

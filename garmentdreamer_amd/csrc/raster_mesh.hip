@@ -27,6 +27,7 @@
 
 #include "../../include/gd_mesh.h"
 #include "../../include/gd_mesh_deform.h"
+#include "raster_common.h"
 
 namespace gd {
 namespace {
@@ -678,6 +679,9 @@ int launched(const char* what)
 }
 
 }  // namespace
+
+int mesh_fail(int code, const char* msg) { return mfail(code, msg); }
+
 }  // namespace gd
 
 extern "C" {
