@@ -58,12 +58,13 @@ template <int VPL>
 __global__ __launch_bounds__(256) void add_layernorm_kernel(const bf16x8* __restrict__ x, const bf16x8* __restrict__ r,
                                                             const bf16x8* __restrict__ w, const bf16x8* __restrict__ b,
                                                             bf16x8* __restrict__ s_out, bf16x8* __restrict__ y,
-                                                            int64_t rows, int vpr /* C / 8 */, float eps)
+                                                            int64_t rows, int vpr /* C / 8 */, float eps,
+                                                            int64_t x_rows /* x holds this many rows, read at row % x_rows */)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const bf16x8* xr = x + row * vpr;
+    const bf16x8* xr = x + (row < x_rows ? row : row % x_rows) * vpr;   // (wave-uniform; no division unless x is shared)
     f2 v[VPL][4];
     f2 sum2 = {0.f, 0.f};
 #pragma unroll
@@ -343,6 +344,121 @@ __global__ __launch_bounds__(256) void conv1x1_c8_kernel(const u32x4* __restrict
     }
 }
 
+// ---- joins of the no-grad UNet: out = a + b (the residual add that ends a Transformer2DModel) or out = [a | b] along
+// the channels (the skip concatenation of an up block), NHWC bf16, with the GroupNorm partial sums of the tensor written.
+// Both results go straight into a GroupNorm whose statistics pass would re-read what this pass just wrote; here the pass
+// that writes the tensor also leaves part[n][C/4][nblk] float2 = {sum, sum of squares} of the ROUNDED bf16 values per
+// 4-channel quad and pixel block -- the layout gd_nn_groupnorm_finish_partials reads (plain stores, fixed order: the
+// statistics do not vary from run to run).  Workgroup = rows x vpp threads (thread <-> one 16-byte channel vector, as in
+// nn_groupnorm.hip), blockIdx.x = pixel block, blockIdx.y = image.  b may hold Nb < N images: image n reads b[n % Nb]
+// (the operand that is shared by the replicas of a classifier-free-guidance batch).
+constexpr int kJoinUnroll = 4;      // independent 16-byte loads per thread and iteration (see gn_stats_kernel)
+constexpr int kJoinMaxThreads = 320;
+
+template <bool CONCAT, bool STATS>
+__global__ __launch_bounds__(kJoinMaxThreads) void join_gn_partials_kernel(const bf16x8* __restrict__ a,
+                                                                           const bf16x8* __restrict__ b,
+                                                                           bf16x8* __restrict__ out, float2* __restrict__ part,
+                                                                           int HW, int vpa, int vpp, int rows, int ppb, int Nb)
+{
+    __shared__ float4 s_red[kJoinMaxThreads];
+    const int n = blockIdx.y, nb = n % Nb;
+    const int tv = threadIdx.x % vpp, tr = threadIdx.x / vpp;
+    const int p0 = blockIdx.x * ppb, p1 = min(HW, p0 + ppb);
+    // the thread's source: ADD reads both operands at its vector; CONCAT reads a (vpa vectors per pixel) or b (the rest)
+    const bool from_b = CONCAT && tv >= vpa;
+    const int vps = CONCAT ? (from_b ? vpp - vpa : vpa) : vpp;      // vectors per pixel of the source
+    const int sv = from_b ? tv - vpa : tv;
+    const bf16x8* src = from_b ? b + (size_t)nb * HW * vps : a + (size_t)n * HW * vps;
+    const bf16x8* bn = b + (size_t)nb * HW * vpp;                    // (ADD only)
+    bf16x8* on = out + (size_t)n * HW * vpp;
+    f2 s[2] = {f2{0.f, 0.f}, f2{0.f, 0.f}}, ss[2] = {f2{0.f, 0.f}, f2{0.f, 0.f}};
+    auto body = [&](const bf16x8& va, const bf16x8& vb, int p) {
+        u32x4 o = __builtin_bit_cast(u32x4, va);
+        if (!CONCAT) {
+            const u32x4 wb = __builtin_bit_cast(u32x4, vb);
+#pragma unroll
+            for (int k = 0; k < 4; k++) o.w[k] = pack2(unpack2(o.w[k]) + unpack2(wb.w[k]));   // fp32 add, one rounding (= aten)
+        }
+        on[(size_t)p * vpp + tv] = __builtin_bit_cast(bf16x8, o);
+        if (STATS) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const f2 f = unpack2(o.w[k]);
+                s[k >> 1] += f;
+                ss[k >> 1] += f * f;
+            }
+        }
+    };
+    int p = p0 + tr;
+    for (; p + (kJoinUnroll - 1) * rows < p1; p += kJoinUnroll * rows) {
+        bf16x8 va[kJoinUnroll], vb[kJoinUnroll];
+#pragma unroll
+        for (int u = 0; u < kJoinUnroll; u++) {
+            va[u] = src[(size_t)(p + u * rows) * vps + sv];
+            if (!CONCAT) vb[u] = bn[(size_t)(p + u * rows) * vpp + tv];
+        }
+#pragma unroll
+        for (int u = 0; u < kJoinUnroll; u++) body(va[u], CONCAT ? va[u] : vb[u], p + u * rows);
+    }
+    for (; p < p1; p += rows) {
+        const bf16x8 va = src[(size_t)p * vps + sv];
+        body(va, CONCAT ? va : bn[(size_t)p * vpp + tv], p);
+    }
+    if (!STATS) return;
+    // the rows of the workgroup, added in a fixed order: quad q = 2 tv + (0 | 1)
+    s_red[threadIdx.x] = float4{s[0].x + s[0].y, ss[0].x + ss[0].y, s[1].x + s[1].y, ss[1].x + ss[1].y};
+    __syncthreads();
+    for (int q = threadIdx.x; q < 2 * vpp; q += blockDim.x) {
+        float sa = 0.f, sb = 0.f;
+        for (int r = 0; r < rows; r++) {
+            const float4 v = s_red[r * vpp + (q >> 1)];
+            sa += (q & 1) ? v.z : v.x;
+            sb += (q & 1) ? v.w : v.y;
+        }
+        part[((size_t)n * (2 * vpp) + q) * gridDim.x + blockIdx.x] = float2{sa, sb};
+    }
+}
+
+// rows x vpp threads and the pixel block of a join: the rule of nn_groupnorm.hip's make_geo (enough workgroups to fill the
+// chip a few times over, at least one pixel per thread row), so a partial sum here spans no more pixels than a statistics
+// workgroup's there
+bool join_geo(int N, int HW, int C, int* vpp, int* rows, int* ppb, int* nblk)
+{
+    if (N <= 0 || N > 65535 || HW <= 0 || C <= 0 || C % 8 || C / 8 > kJoinMaxThreads) return false;
+    *vpp = C / 8;
+    *rows = *vpp >= 256 ? 1 : 256 / *vpp;
+    int p = 128;
+    while (p > *rows && (long)((HW + p - 1) / p) * N < 2048) p >>= 1;
+    if (p < *rows) p = *rows;
+    *ppb = p;
+    *nblk = (HW + p - 1) / p;
+    return true;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <bool CONCAT>
+int join_launch(void* stream, const void* a, const void* b, void* out, float* part, int N, int Nb, int HW, int C0, int C1)
+{
+    const int C = CONCAT ? C0 + C1 : C0;
+    int vpp, rows, ppb, nblk;
+    if (!a || !b || !out) return fail(GD_NN_ERR_INVALID_ARG, "join: null pointer");
+    if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return fail(GD_NN_ERR_INVALID_ARG, "join: tensors must be 16-byte aligned");
+    if (C0 <= 0 || C0 % 8 || (CONCAT && (C1 <= 0 || C1 % 8)) || !join_geo(N, HW, C, &vpp, &rows, &ppb, &nblk))
+        return fail(GD_NN_ERR_INVALID_ARG, "join: need channel counts that are multiples of 8, C <= 2560, N <= 65535");
+    if (Nb <= 0 || Nb > N || N % Nb) return fail(GD_NN_ERR_INVALID_ARG, "join: the images of b must divide N");
+    if ((int64_t)N * HW * C >= (int64_t)1 << 40) return fail(GD_NN_ERR_INVALID_ARG, "join: tensor too large");
+    const dim3 grid(nblk, N), block(rows * vpp);
+    if (part)
+        hipLaunchKernelGGL((join_gn_partials_kernel<CONCAT, true>), grid, block, 0, (hipStream_t)stream, (const bf16x8*)a,
+                           (const bf16x8*)b, (bf16x8*)out, (float2*)part, HW, C0 / 8, vpp, rows, ppb, Nb);
+    else
+        hipLaunchKernelGGL((join_gn_partials_kernel<CONCAT, false>), grid, block, 0, (hipStream_t)stream, (const bf16x8*)a,
+                           (const bf16x8*)b, (bf16x8*)out, (float2*)nullptr, HW, C0 / 8, vpp, rows, ppb, Nb);
+    return launch_status("join: launch failed");
+}
+
 }  // namespace
 
 extern "C" {
@@ -364,10 +480,19 @@ int gd_nn_geglu_forward(void* stream, const void* x, void* y, int64_t rows, int 
 int gd_nn_add_layernorm_forward(void* stream, const void* x, const void* residual, const void* weight, const void* bias,
                                 float eps, void* sum_out, void* y, int64_t rows, int C)
 {
+    return gd_nn_add_layernorm_forward_bcast(stream, x, residual, weight, bias, eps, sum_out, y, rows, C, rows);
+}
+
+int gd_nn_add_layernorm_forward_bcast(void* stream, const void* x, const void* residual, const void* weight,
+                                      const void* bias, float eps, void* sum_out, void* y, int64_t rows, int C,
+                                      int64_t x_rows)
+{
     if (!x || !weight || !bias || !y) return fail(GD_NN_ERR_INVALID_ARG, "add_layernorm: null pointer");
     if (rows <= 0 || C <= 0 || C % 8 || C > 64 * 8 * 4)
         return fail(GD_NN_ERR_INVALID_ARG, "add_layernorm: need C % 8 == 0 and C <= 2048");
     if (sum_out && !residual) return fail(GD_NN_ERR_INVALID_ARG, "add_layernorm: sum_out without residual");
+    if (x_rows <= 0 || x_rows > rows || rows % x_rows || (x_rows != rows && !residual))
+        return fail(GD_NN_ERR_INVALID_ARG, "add_layernorm: x_rows must divide rows (and a shared x needs a residual)");
     const int vpr = C / 8;
     const int vpl = (vpr + 63) / 64;
     const int64_t blocks = (rows + 3) / 4;
@@ -375,13 +500,31 @@ int gd_nn_add_layernorm_forward(void* stream, const void* x, const void* residua
 #define GD_LN(V_)                                                                                                      \
     hipLaunchKernelGGL(add_layernorm_kernel<V_>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,            \
                        (const bf16x8*)x, (const bf16x8*)residual, (const bf16x8*)weight, (const bf16x8*)bias,          \
-                       (bf16x8*)sum_out, (bf16x8*)y, rows, vpr, eps)
+                       (bf16x8*)sum_out, (bf16x8*)y, rows, vpr, eps, x_rows)
     if (vpl == 1) GD_LN(1);
     else if (vpl == 2) GD_LN(2);
     else if (vpl == 3) GD_LN(3);
     else GD_LN(4);
 #undef GD_LN
     return launch_status("add_layernorm: launch failed");
+}
+
+size_t gd_nn_join_stat_rows(int N, int HW, int C)
+{
+    int vpp, rows, ppb, nblk;
+    return join_geo(N, HW, C, &vpp, &rows, &ppb, &nblk) ? (size_t)nblk : 0;
+}
+
+int gd_nn_add_gn_partials(void* stream, const void* a, const void* b, void* out, float* stat_part, int N, int Nb, int HW,
+                          int C)
+{
+    return join_launch<false>(stream, a, b, out, stat_part, N, Nb, HW, C, 0);
+}
+
+int gd_nn_concat_gn_partials(void* stream, const void* a, const void* b, void* out, float* stat_part, int N, int Nb, int HW,
+                             int C0, int C1)
+{
+    return join_launch<true>(stream, a, b, out, stat_part, N, Nb, HW, C0, C1);
 }
 
 int gd_nn_geglu_backward(void* stream, const void* x, const void* dy, void* dx, int64_t rows, int inner)

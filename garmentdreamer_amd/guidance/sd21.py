@@ -57,8 +57,10 @@ _FP8_ACTIVE = [None]   # the nn_ops.Fp8State of the UNet whose no-grad forward i
 
 
 def _gn(norm: nn.GroupNorm, x, silu: bool):
-    """GroupNorm (+SiLU): fused NHWC HIP kernel on the GPU (nn_ops), torch ops on CPU."""
-    return group_norm_silu(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu)
+    """GroupNorm (+SiLU): fused NHWC HIP kernel on the GPU (nn_ops), torch ops on CPU.  Statistics that came with x (left
+    by the join that wrote it: nn_ops.add_join / concat_join) replace the kernel's own statistics pass."""
+    mr = nn_ops.gn_stats_of(x, norm.num_groups, norm.eps) if x.is_cuda else None
+    return group_norm_silu(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu, mean_rstd=mr)
 
 
 def _conv3(conv: nn.Conv2d, x, image_bias=None, residual=None):
@@ -246,21 +248,32 @@ class Attention(nn.Module):
             "to_out_lora": LoRALinearLayer(inner, self.to_out[0].out_features, rank)})
         return self.lora
 
-    def forward(self, x, context=None):
+    def forward(self, x, context=None, reps: int = 1):
+        """``reps`` > 1 (cross-attention of a shared guidance prefix, UNet2DConditionModel.forward(shared_reps=)): x holds one
+        copy of the samples, the context reps copies -- entry b of the result attends with the query of x[b % len(x)]."""
         B, N, _ = x.shape
         kv = context_vt = None
         if isinstance(context, ContextProjections):
             kv = context.kv.get(id(self)) if self.lora is None else None
             context_vt = context.vt
             context = context.context
+        if reps > 1 and kv is None:
+            x = x.repeat(reps, 1, 1)       # no projected context to share a query against: the plain batch
+            B, reps = B * reps, 1
         ctx = x if context is None else context
         if kv is not None:
-            q, (k, v) = _lin(self.to_q, x), kv
+            with nn_ops.route_batch_shared(reps):
+                q = _lin(self.to_q, x)
+            k, v = kv
             vt = context_vt.get(id(self)) if context_vt is not None else None
             if vt is not None and N >= 256 and _CTX_VT and q.shape[-1] == 64 * self.heads and not torch.is_grad_enabled():
-                q4, k4 = q.view(B, N, self.heads, 64), k.view(B, k.shape[1], self.heads, 64)
-                if nn_ops._attention_d64_layout_ok(q4, k4, k4):
+                q4, k4 = q.view(B, N, self.heads, 64), k.view(B * reps, k.shape[1], self.heads, 64)
+                if nn_ops._attention_d64_layout_ok(q4, k4[:B], k4[:B]):
+                    # (a shared query is read by one launch per replica: no repeated q exists)
                     return _lin(self.to_out[0], nn_ops.attention_d64_vt_strided(q4, k4, vt, k.shape[1]))
+            if reps > 1:
+                q = q.repeat(reps, 1, 1)
+                B = B * reps
         elif _FUSED_QKV and context is None and self.lora is None and x.is_cuda and self.to_q.bias is None and \
                 not self.to_q.weight.requires_grad and not torch.is_grad_enabled():
             # frozen self-attention: ONE [C, 2C] projection for q | k (the attention kernel reads the two strided views)
@@ -366,12 +379,16 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ff = FeedForward(dim)
 
-    def forward(self, x, context, defer_ff_bias: bool = False):
+    def forward(self, x, context, defer_ff_bias: bool = False, reps: int = 1):
         # x = x + attn1(norm1(x)); x = x + attn2(norm2(x), ctx); x = x + ff(norm3(x)) with each residual add fused
-        # into the LayerNorm that follows it (nn_ops.add_layer_norm; plain torch ops when gradients are needed)
-        _, n = add_layer_norm(x, None, self.norm1)
-        x, n = add_layer_norm(x, self.attn1(n), self.norm2)
-        x, n = add_layer_norm(x, self.attn2(n, context), self.norm3)
+        # into the LayerNorm that follows it (nn_ops.add_layer_norm; plain torch ops when gradients are needed).
+        # reps > 1: x is ONE copy of the samples of a guidance batch whose `reps` copies differ only in the context -- the
+        # self-attention runs once, and the residual stream widens to reps copies where the cross-attention's output
+        # (one per context) is added to it (add_layer_norm reads the shared x at row % len(x))
+        with nn_ops.route_batch_shared(reps):
+            _, n = add_layer_norm(x, None, self.norm1)
+            x, n = add_layer_norm(x, self.attn1(n), self.norm2)
+        x, n = add_layer_norm(x, self.attn2(n, context, reps=reps), self.norm3)
         if defer_ff_bias:
             # last residual inside the GEMM (beta = 1): x + gelu-gated(n) @ W2^T; the caller owes the constant b2
             g = self.ff.net[0](n)
@@ -396,23 +413,29 @@ class Transformer2DModel(nn.Module):
             self._fold_key = key
         return self._fold_bias
 
-    def forward(self, x, context):
+    def forward(self, x, context, next_norm=None, reps: int = 1):
+        """``next_norm``: the GroupNorm that consumes the result, if the caller knows it (its statistics then come out of the
+        closing residual add, nn_ops.add_join).  ``reps`` > 1: x is the one copy of a shared guidance prefix; the result
+        has reps copies (BasicTransformerBlock.forward)."""
         B, C, H, W = x.shape
-        h = _gn(self.norm, x, False)
-        h = h.permute(0, 2, 3, 1).reshape(B, H * W, C)  # free for channels_last activations
-        h = _lin(self.proj_in, h)
+        with nn_ops.route_batch_shared(reps):
+            h = _gn(self.norm, x, False)
+            h = h.permute(0, 2, 3, 1).reshape(B, H * W, C)  # free for channels_last activations
+            h = _lin(self.proj_in, h)
         if len(self.transformer_blocks) == 1 and h.is_cuda and not torch.is_grad_enabled() and \
                 not self.proj_out.weight.requires_grad:
             # frozen inference: the block's feed-forward output bias b2 is a constant added right before proj_out,
             # so it moves into proj_out's bias (W_out b2 + b_out) and the residual add moves into the GEMM
-            h = self.transformer_blocks[0](h, context, defer_ff_bias=True)
+            h = self.transformer_blocks[0](h, context, defer_ff_bias=True, reps=reps)
             h = _lin(self.proj_out, h, self._folded_out_bias(h.dtype))
         else:
-            for blk in self.transformer_blocks:
-                h = blk(h, context)
+            for i, blk in enumerate(self.transformer_blocks):
+                h = blk(h, context, reps=reps if i == 0 else 1)
             h = self.proj_out(h)
-        h = h.reshape(B, H, W, C).permute(0, 3, 1, 2)
-        return h + x
+        h = h.reshape(B * reps, H, W, C).permute(0, 3, 1, 2)
+        if h.is_cuda and not torch.is_grad_enabled():
+            return nn_ops.add_join(h, x, next_norm)      # (x may be the shared copy: read at image n % len(x))
+        return h + (x if reps == 1 else x.repeat(reps, 1, 1, 1))
 
 
 class Downsample2D(nn.Module):
@@ -451,11 +474,21 @@ class _DownBlock(nn.Module):
             [Transformer2DModel(out_ch, heads, out_ch // heads, cross_dim) for _ in range(n_layers)]) if attn else None
         self.downsamplers = nn.ModuleList([Downsample2D(out_ch)]) if down else None
 
-    def forward(self, x, temb, context, skips):
+    def forward(self, x, temb, context, skips, reps: int = 1, temb_shared=None):
+        """``reps`` > 1 (the first block of a shared guidance prefix): x and ``temb_shared`` hold one copy of the samples; the
+        first ResnetBlock runs on it and the first transformer widens the batch to reps copies at its cross-attention."""
+        n = len(self.resnets)
         for i, res in enumerate(self.resnets):
-            x = res(x, temb)
+            if reps > 1 and i == 0:
+                with nn_ops.route_batch_shared(reps):
+                    x = res(x, temb_shared)
+                if self.attentions is None:
+                    x = x.repeat(reps, 1, 1, 1)
+            else:
+                x = res(x, temb)
             if self.attentions is not None:
-                x = self.attentions[i](x, context)
+                x = self.attentions[i](x, context, next_norm=self.resnets[i + 1].norm1 if i + 1 < n else None,
+                                       reps=reps if i == 0 else 1)
             skips.append(x)
         if self.downsamplers is not None:
             x = self.downsamplers[0](x)
@@ -476,12 +509,21 @@ class _UpBlock(nn.Module):
             [Transformer2DModel(out_ch, heads, out_ch // heads, cross_dim) for _ in range(n_layers)]) if attn else None
         self.upsamplers = nn.ModuleList([Upsample2D(out_ch)]) if up else None
 
-    def forward(self, x, temb, context, skips):
+    def forward(self, x, temb, context, skips, next_norm=None):
+        """``next_norm``: the GroupNorm that consumes the block's result (the UNet's conv_norm_out after the last block)."""
+        n = len(self.resnets)
         for i, res in enumerate(self.resnets):
-            x = torch.cat([x, skips.pop()], dim=1)
+            skip = skips.pop()
+            if x.is_cuda and not torch.is_grad_enabled():
+                # the concatenation leaves norm1's statistics; a skip kept at one copy of a shared prefix is read by image % copy
+                x = nn_ops.concat_join(x, skip, res.norm1)
+            else:
+                x = torch.cat([x, skip if skip.shape[0] == x.shape[0] else skip.repeat(x.shape[0] // skip.shape[0], 1, 1, 1)],
+                              dim=1)
             x = res(x, temb)
             if self.attentions is not None:
-                x = self.attentions[i](x, context)
+                x = self.attentions[i](x, context,
+                                       next_norm=next_norm if i + 1 == n and self.upsamplers is None else None)
         if self.upsamplers is not None:
             x = self.upsamplers[0](x)
         return x
@@ -591,18 +633,21 @@ class UNet2DConditionModel(nn.Module):
             voff += c
         return ContextProjections(ctx, kv, vt)
 
-    def _project_temb(self, temb):
-        """All blocks' per-image conv1 biases in one GEMM (``TembProjections``).  The projection weights must be frozen; the
+    def _project_temb(self, temb, reps: int = 1):
+        """``reps`` > 1: temb holds one copy of a shared guidance batch; returns (projections of that copy, projections
+        expanded once to reps copies -- [reps * V, total] is a few KB).  reps == 1: the projections alone.
+        All blocks' per-image conv1 biases in one GEMM (``TembProjections``).  The projection weights must be frozen; the
         time embedding itself may need a gradient (the LoRA UNet's camera / shading embedding is part of it): the GEMM and the
         SiLU before it then run under autograd ONCE, the blocks take ``torch.split`` views of the result, and the backward pass
         is one concatenation of the 22 bias gradients, one GEMM and one SiLU backward instead of 22 of each plus 21
         accumulations into the embedding's gradient (round 5; ``GD_TEMB_TRAIN_CAT=0`` = per block as before)."""
         train = torch.is_grad_enabled() and temb.requires_grad
+        plain = (temb, temb.repeat(reps, 1)) if reps > 1 else temb
         if not temb.is_cuda or (train and not _TEMB_TRAIN_CAT):
-            return temb
+            return plain
         blocks = [m for m in self.modules() if isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None]
         if not blocks or any(b.time_emb_proj.weight.requires_grad or b.conv1.bias.requires_grad for b in blocks):
-            return temb
+            return plain
         first = blocks[0].time_emb_proj.weight
         key = (first.data_ptr(), temb.dtype, len(blocks)) + tuple(
             t._version for b in blocks for t in (b.time_emb_proj.weight, b.time_emb_proj.bias, b.conv1.bias))
@@ -617,12 +662,17 @@ class UNet2DConditionModel(nn.Module):
             return TembProjections(temb, {id(b): p for b, p in zip(blocks, parts)})
         with torch.no_grad():
             allp = _lib_linear(F.silu(temb), cache[1], cache[2])
-        out, off = {}, 0
-        for b in blocks:
-            c = b.time_emb_proj.out_features
-            out[id(b)] = allp[:, off:off + c]
-            off += c
-        return TembProjections(temb, out)
+
+        def slices(t, allp):
+            out, off = {}, 0
+            for b in blocks:
+                c = b.time_emb_proj.out_features
+                out[id(b)] = allp[:, off:off + c]
+                off += c
+            return TembProjections(t, out)
+        if reps > 1:
+            return slices(temb, allp), slices(temb.repeat(reps, 1), allp.repeat(reps, 1))
+        return slices(temb, allp)
 
     fp8 = None    # nn_ops.Fp8State: e4m3 convolutions in the no-grad forward (enable_fp8); None = bf16 everywhere
 
@@ -634,33 +684,66 @@ class UNet2DConditionModel(nn.Module):
         self.fp8 = state if state is not None else Fp8State()
         return self.fp8
 
-    def forward(self, sample, timestep, encoder_hidden_states, **kwargs):
+    supports_shared_reps = True     # forward(..., shared_reps=r): what a caller checks before it passes the argument
+
+    def forward(self, sample, timestep, encoder_hidden_states, shared_reps: int = 1, **kwargs):
+        """``shared_reps`` = r > 1: the batch is r copies of ``sample`` / ``timestep`` ([V, ...], passed ONCE) that differ only
+        in ``encoder_hidden_states`` ([r * V, 77, D]: copy j of sample v at row j * V + v) -- classifier-free guidance.  The
+        result is that of ``forward(cat([sample] * r), cat([timestep] * r), encoder_hidden_states)``; everything ahead of
+        the first cross-attention's key/value read (conv_in, the time embedding, the first ResnetBlock, the first
+        transformer up to the cross-attention's query) is computed once.  The copies are identical because the CALLER
+        states it by passing one tensor -- the data are never compared."""
         if self.fp8 is not None and not torch.is_grad_enabled() and sample.is_cuda:
             _FP8_ACTIVE[0] = self.fp8
             try:
-                return self._forward(sample, timestep, encoder_hidden_states, **kwargs)
+                return self._forward(sample, timestep, encoder_hidden_states, shared_reps, **kwargs)
             finally:
                 _FP8_ACTIVE[0] = None
-        return self._forward(sample, timestep, encoder_hidden_states, **kwargs)
+        return self._forward(sample, timestep, encoder_hidden_states, shared_reps, **kwargs)
 
-    def _forward(self, sample, timestep, encoder_hidden_states, **kwargs):
+    def _shared_prefix_ok(self, sample) -> bool:
+        """The shared prefix runs in the frozen no-grad GPU forward of the plain UNet; every other call (CPU, autograd, a
+        subclass whose extra embedding is per batch entry) gets the repeated batch, as before."""
+        return (sample.is_cuda and not torch.is_grad_enabled() and not self.conv_in.weight.requires_grad
+                and type(self).extra_embedding is UNet2DConditionModel.extra_embedding
+                and self.down_blocks[0].attentions is not None)
+
+    def _forward(self, sample, timestep, encoder_hidden_states, shared_reps: int = 1, **kwargs):
         dtype = self.conv_in.weight.dtype
+        reps = int(shared_reps)
+        if reps < 1 or encoder_hidden_states.shape[0] != sample.shape[0] * reps:
+            raise ValueError(f"shared_reps={reps}: {sample.shape[0]} samples need {sample.shape[0] * max(reps, 1)} contexts, "
+                             f"got {encoder_hidden_states.shape[0]}")
+        if reps > 1 and not self._shared_prefix_ok(sample):
+            sample = torch.cat([sample] * reps, dim=0)
+            if timestep.dim() > 0:
+                timestep = torch.cat([timestep] * reps)
+            reps = 1
         if timestep.dim() == 0:
             timestep = timestep[None].expand(sample.shape[0])
-        temb = self.time_embedding(sinusoidal_timestep_embedding(timestep, self.block_out_channels[0]).to(dtype))
-        extra = self.extra_embedding(sample.shape[0], **kwargs)
-        if extra is not None:
-            temb = temb + extra.to(dtype)
-        temb = self._project_temb(temb)
-        x = conv3x3_small_cin(sample.to(dtype).contiguous(memory_format=torch.channels_last), self.conv_in.weight,
-                              self.conv_in.bias)
+        with nn_ops.route_batch_shared(reps):
+            temb = self.time_embedding(sinusoidal_timestep_embedding(timestep, self.block_out_channels[0]).to(dtype))
+            extra = self.extra_embedding(sample.shape[0], **kwargs)
+            if extra is not None:
+                temb = temb + extra.to(dtype)
+            temb_shared = None
+            if reps > 1:
+                temb_shared, temb = self._project_temb(temb, reps)
+            else:
+                temb = self._project_temb(temb)
+            x = conv3x3_small_cin(sample.to(dtype).contiguous(memory_format=torch.channels_last), self.conv_in.weight,
+                                  self.conv_in.bias)
         ctx = self._project_context(encoder_hidden_states.to(dtype))
-        skips = [x]
-        for blk in self.down_blocks:
-            x = blk(x, temb, ctx, skips)
+        skips = [x]           # (reps > 1: conv_in's output stays at one copy; the last up block's concatenation shares it)
+        for i, blk in enumerate(self.down_blocks):
+            if i == 0 and reps > 1:
+                x = blk(x, temb, ctx, skips, reps=reps, temb_shared=temb_shared)
+            else:
+                x = blk(x, temb, ctx, skips)
         x = self.mid_block(x, temb, ctx)
-        for blk in self.up_blocks:
-            x = blk(x, temb, ctx, skips)
+        last = len(self.up_blocks) - 1
+        for i, blk in enumerate(self.up_blocks):
+            x = blk(x, temb, ctx, skips, next_norm=self.conv_norm_out if i == last else None)
         return _conv3(self.conv_out, _gn(self.conv_norm_out, x, True))
 
 

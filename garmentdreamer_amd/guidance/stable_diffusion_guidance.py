@@ -29,6 +29,10 @@ import torch.nn.functional as F
 from .. import _runtime_env, nn_ops
 from . import sd21
 
+import os as _os
+# A/B toggle: =0 hands the UNet the repeated guidance batch (no shared prefix); same-box timing in tools/, never set in tests
+_SHARED_PREFIX = _os.environ.get("GD_SHARED_PREFIX", "1") != "0"
+
 
 def C(value: Any, epoch: int, global_step: int) -> float:
     """threestudio's schedule literal ``[start_step, v0, v1, end_step]``
@@ -141,7 +145,16 @@ class StableDiffusionGuidance(nn.Module):
         self.min_step = int(self.num_train_timesteps * min_step_percent)
         self.max_step = int(self.num_train_timesteps * max_step_percent)
 
-    def forward_unet(self, latents, t, encoder_hidden_states):
+    def _shared_reps(self, reps: int) -> dict:
+        """Keyword for ``forward_unet`` at the call sites that build the UNet batch as ``reps`` copies of one tensor: a UNet
+        that takes ``shared_reps`` (sd21.UNet2DConditionModel) gets the tensor once and computes the part ahead of the
+        first cross-attention once; any other UNet gets the repeated batch."""
+        return {"shared_reps": reps} if _SHARED_PREFIX and reps > 1 and getattr(self.unet, "supports_shared_reps", False) else {}
+
+    def forward_unet(self, latents, t, encoder_hidden_states, shared_reps: int = 1):
+        """``shared_reps`` = r > 1: ``latents`` / ``t`` are ONE copy of a batch made of r identical copies (the caller built
+        it that way), ``encoder_hidden_states`` has r entries per sample; the result has r * len(latents) entries."""
+        kw = {"shared_reps": int(shared_reps)} if shared_reps > 1 else {}
         input_dtype = latents.dtype
         # the reference casts t to its fp16 weights dtype (:155), which holds every timestep < 2048 exactly; bf16
         # would round t > 256 to a multiple of 2 or 4, so with bf16 weights the timestep stays fp32
@@ -150,7 +163,7 @@ class StableDiffusionGuidance(nn.Module):
         fp8 = getattr(self.unet, "fp8", None)
         if fp8 is not None and not self._fp8_calibrated and not torch.is_grad_enabled():
             # one eager bf16 forward on the real inputs records every fp8 site's activation range
-            out = self.unet(x, tt, encoder_hidden_states=ctx).to(input_dtype)
+            out = self.unet(x, tt, encoder_hidden_states=ctx, **kw).to(input_dtype)
             self._fp8_calib_done += 1
             if self._fp8_calib_done >= max(1, int(self.cfg.fp8_calibration_steps)):
                 fp8.mode = "run"
@@ -158,17 +171,18 @@ class StableDiffusionGuidance(nn.Module):
             return out
         if self.cfg.use_hip_graphs and x.is_cuda and not torch.is_grad_enabled():
             try:
-                return self._graphed_unet(x, tt, ctx).to(input_dtype)
+                return self._graphed_unet(x, tt, ctx, **kw).to(input_dtype)
             except RuntimeError as e:      # capture refused (driver / allocator state): keep running, eagerly
                 self._graphs_failed(e)
-        return self.unet(x, tt, encoder_hidden_states=ctx).to(input_dtype)
+        return self.unet(x, tt, encoder_hidden_states=ctx, **kw).to(input_dtype)
 
     def may_capture(self, batch_size: int) -> bool:
         """True while a call on `batch_size` images may still CAPTURE a hipGraph (the caller then keeps no collective of its
         process in flight across it): graphs are on and the UNet / VAE graph of that batch shape does not exist yet."""
         if not self.cfg.use_hip_graphs:
             return False
-        have_u = any(k[0][0] in (2 * batch_size, 4 * batch_size) for k in self._unet_graphs)
+        have_u = any(k[1][0] in (2 * batch_size, 4 * batch_size) for k in self._unet_graphs)   # (the context's batch: the
+        # samples of a shared-prefix graph are one copy)
         have_v = any(k[0] == batch_size for k in self._vae_graphs)
         return not (have_u and have_v)
 
@@ -184,8 +198,9 @@ class StableDiffusionGuidance(nn.Module):
         nn_ops.reset_workspaces()      # an aborted capture may have left a statistics workspace mid-update
 
     # ---- hipGraph replay ----------------------------------------------------------------------
-    def _graphed_unet(self, x, t, ctx):
-        key = (tuple(x.shape), tuple(ctx.shape))
+    def _graphed_unet(self, x, t, ctx, **kw):
+        """``kw``: {} or {"shared_reps": r} -- part of the graph's key (static inputs: one copy of the samples, r contexts)."""
+        key = (tuple(x.shape), tuple(ctx.shape)) + tuple(sorted(kw.items()))
         entry = self._unet_graphs.get(key)
         if entry is None:
             sx, st, sc = x.clone(), t.clone(), ctx.clone()
@@ -193,11 +208,11 @@ class StableDiffusionGuidance(nn.Module):
             side.wait_stream(torch.cuda.current_stream(x.device))
             with torch.cuda.stream(side), torch.no_grad():
                 for _ in range(2):   # warm-up outside capture: library solver selection, weight caches
-                    self.unet(sx, st, encoder_hidden_states=sc)
+                    self.unet(sx, st, encoder_hidden_states=sc, **kw)
             torch.cuda.current_stream(x.device).wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with _runtime_env.capture_guard(), torch.cuda.graph(g), torch.no_grad():
-                out = self.unet(sx, st, encoder_hidden_states=sc)
+                out = self.unet(sx, st, encoder_hidden_states=sc, **kw)
             entry = self._unet_graphs[key] = (g, sx, st, sc, out)
         g, sx, st, sc, out = entry
         sx.copy_(x)
@@ -258,9 +273,13 @@ class StableDiffusionGuidance(nn.Module):
                 if noise is None:
                     noise = torch.randn_like(latents)
                 latents_noisy = self.scheduler.add_noise(latents, noise, t)
+                share = self._shared_reps(4)
                 with nn_ops.route_batch(4, 4 * batch_size):
-                    noise_pred = self.forward_unet(torch.cat([latents_noisy] * 4, dim=0), torch.cat([t] * 4),
-                                                   encoder_hidden_states=text_embeddings)
+                    if share:
+                        noise_pred = self.forward_unet(latents_noisy, t, encoder_hidden_states=text_embeddings, **share)
+                    else:
+                        noise_pred = self.forward_unet(torch.cat([latents_noisy] * 4, dim=0), torch.cat([t] * 4),
+                                                       encoder_hidden_states=text_embeddings)
             noise_pred_text = noise_pred[:batch_size]
             noise_pred_uncond = noise_pred[batch_size:batch_size * 2]
             noise_pred_neg = noise_pred[batch_size * 2:]
@@ -279,10 +298,13 @@ class StableDiffusionGuidance(nn.Module):
                 if noise is None:
                     noise = torch.randn_like(latents)
                 latents_noisy = self.scheduler.add_noise(latents, noise, t)
-                latent_model_input = torch.cat([latents_noisy] * 2, dim=0)
+                share = self._shared_reps(2)
                 with nn_ops.route_batch(2, 2 * batch_size):
-                    noise_pred = self.forward_unet(latent_model_input, torch.cat([t] * 2),
-                                                   encoder_hidden_states=text_embeddings)
+                    if share:      # the two halves are one tensor: handed over once (sd21.UNet2DConditionModel.forward)
+                        noise_pred = self.forward_unet(latents_noisy, t, encoder_hidden_states=text_embeddings, **share)
+                    else:
+                        noise_pred = self.forward_unet(torch.cat([latents_noisy] * 2, dim=0), torch.cat([t] * 2),
+                                                       encoder_hidden_states=text_embeddings)
             noise_pred_text, noise_pred_uncond = noise_pred.chunk(2)
             noise_pred = noise_pred_text + self.cfg.guidance_scale * (noise_pred_text - noise_pred_uncond)
 
@@ -324,9 +346,13 @@ class StableDiffusionGuidance(nn.Module):
             y = latents
             zs = y + sigma * noise
             scaled_zs = zs / torch.sqrt(1 + sigma ** 2)
+            share = self._shared_reps(reps)
             with nn_ops.route_batch(reps, reps * batch_size):
-                noise_pred = self.forward_unet(torch.cat([scaled_zs] * reps, dim=0), torch.cat([t] * reps),
-                                               encoder_hidden_states=text_embeddings)
+                if share:
+                    noise_pred = self.forward_unet(scaled_zs, t, encoder_hidden_states=text_embeddings, **share)
+                else:
+                    noise_pred = self.forward_unet(torch.cat([scaled_zs] * reps, dim=0), torch.cat([t] * reps),
+                                                   encoder_hidden_states=text_embeddings)
         if use_perp_neg:
             noise_pred_text = noise_pred[:batch_size]
             noise_pred_uncond = noise_pred[batch_size:batch_size * 2]
@@ -421,10 +447,15 @@ class StableDiffusionGuidance(nn.Module):
         batch_size = latents_noisy.shape[0]
         reps = 4 if use_perp_neg else 2
         from .. import nn_ops
+        share = self._shared_reps(reps)
         with nn_ops.route_batch(reps, reps * batch_size):     # (read under batch-invariant kernel selection only)
-            noise_pred = self.forward_unet(torch.cat([latents_noisy] * reps, dim=0),
-                                           torch.cat([t.reshape(1)] * reps).to(self.device),
-                                           encoder_hidden_states=text_embeddings)
+            if share:
+                noise_pred = self.forward_unet(latents_noisy, t.reshape(1).to(self.device),
+                                               encoder_hidden_states=text_embeddings, **share)
+            else:
+                noise_pred = self.forward_unet(torch.cat([latents_noisy] * reps, dim=0),
+                                               torch.cat([t.reshape(1)] * reps).to(self.device),
+                                               encoder_hidden_states=text_embeddings)
         if use_perp_neg:
             noise_pred_text = noise_pred[:batch_size]
             noise_pred_uncond = noise_pred[batch_size:batch_size * 2]

@@ -95,6 +95,10 @@ SIGNATURES = {
     "gd_nn_softmax_rows_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i]),
     "gd_nn_layernorm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float]),
     "gd_nn_add_layernorm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_int64, _i]),
+    "gd_nn_add_layernorm_forward_bcast": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_int64, _i, C.c_int64]),
+    "gd_nn_join_stat_rows": (C.c_size_t, [_i, _i, _i]),
+    "gd_nn_add_gn_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "gd_nn_concat_gn_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "gd_nn_attention_ws_bytes": (C.c_size_t, [_i, _i, _i]),
     "gd_nn_attention_d64_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i,
                                          C.c_int64, _i, C.c_int64, _i, _f, _i]),
@@ -245,18 +249,20 @@ def _is_nhwc_bf16(x):
 
 class _GroupNormSiLU(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, groups, eps, silu):
+    def forward(ctx, x, weight, bias, groups, eps, silu, mean_rstd=None):
         N, Cc, H, W = x.shape
         L = lib()
         y = torch.empty_like(x, memory_format=torch.channels_last)
-        ws = _gn_workspace(x, N, groups)
-        mr = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
+        # mean_rstd given: the statistics came with the tensor (a join's or a convolution's partial sums) -- apply pass only
+        ws = _gn_workspace(x, N, groups) if mean_rstd is None else None
+        mr = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device) if mean_rstd is None else mean_rstd
         w, b = weight.contiguous(), bias.contiguous()
         with torch.cuda.device(x.device):
             stream = torch.cuda.current_stream(x.device).cuda_stream
             _check(L.gd_nn_groupnorm_silu_forward(stream, x.data_ptr(), y.data_ptr(), w.data_ptr(), b.data_ptr(), N,
-                                                  H * W, Cc, groups, float(eps), int(silu), ws.data_ptr(),
-                                                  mr.data_ptr()), "gd_nn_groupnorm_silu_forward")
+                                                  H * W, Cc, groups, float(eps), int(silu),
+                                                  None if ws is None else ws.data_ptr(), mr.data_ptr()),
+                   "gd_nn_groupnorm_silu_forward")
         ctx.save_for_backward(x, w, b, mr)
         ctx.groups, ctx.silu = groups, silu
         return y
@@ -278,7 +284,7 @@ class _GroupNormSiLU(torch.autograd.Function):
                                                    mr.data_ptr(), dx.data_ptr(), N, H * W, Cc, ctx.groups,
                                                    int(ctx.silu), ws.data_ptr(), sums.data_ptr(), None),
                    "gd_nn_groupnorm_silu_backward")
-        return dx, None, None, None, None, None
+        return dx, None, None, None, None, None, None
 
 
 # GD_NN_GN_SMALL=0: the two-pass GroupNorm also where the one-launch form applies (A/B timing in tools/; never set in tests)
@@ -344,8 +350,19 @@ class _GroupNormSiLUSmall(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
-def group_norm_silu(x, weight, bias, groups: int, eps: float, silu: bool = True):
-    """``silu(group_norm(x))`` (or just group_norm).  HIP kernel for bf16 NHWC tensors on the GPU."""
+def gn_stats_of(x, groups: int, eps: float):
+    """The finished ``mean_rstd`` that rides on ``x`` (``_gd_gn_stats``: left by a join or a frozen ResnetBlock for the
+    GroupNorm of exactly these groups / eps, and x not written since), or None."""
+    tag = getattr(x, "_gd_gn_stats", None)
+    if tag is not None and tag[1:] == (groups, eps, x._version):
+        return tag[0]
+    return None
+
+
+def group_norm_silu(x, weight, bias, groups: int, eps: float, silu: bool = True, mean_rstd=None):
+    """``silu(group_norm(x))`` (or just group_norm).  HIP kernel for bf16 NHWC tensors on the GPU.  ``mean_rstd``: the
+    finished statistics of x ([N * groups * 2] fp32, e.g. ``gn_stats_of``): the two-pass form then skips its statistics
+    pass; the one-launch form and the torch ops compute their own."""
     if x.is_cuda:
         if weight.requires_grad or bias.requires_grad:
             raise RuntimeError("group_norm_silu HIP kernel computes input gradients only (frozen weights)")
@@ -358,11 +375,105 @@ def group_norm_silu(x, weight, bias, groups: int, eps: float, silu: bool = True)
                     return _GroupNormSiLUSmall.apply(x, weight, bias, groups, eps, silu)
             elif small and _GN_FUSED_SMALL:
                 return _gn_fused_small(x, weight, bias, groups, eps, silu)
-            return _GroupNormSiLU.apply(x, weight, bias, groups, eps, silu)
+            if mean_rstd is not None and (mean_rstd.dtype != torch.float32 or mean_rstd.numel() != x.shape[0] * groups * 2
+                                          or not mean_rstd.is_contiguous() or mean_rstd.device != x.device):
+                raise ValueError("group_norm_silu: mean_rstd must be contiguous fp32 [N * groups * 2] on x's device")
+            return _GroupNormSiLU.apply(x, weight, bias, groups, eps, silu, mean_rstd)
         # fp32 GPU runs (parity checks of the bf16 path) use torch's ops
         _note_fallback("group_norm_silu", x, "needs a 4-D tensor with C % 8 == 0")
     y = F.group_norm(x, groups, weight, bias, eps)
     return F.silu(y) if silu else y
+
+
+# ---------------------------------------------------------------------------------------------
+# joins of the no-grad UNet: residual add / skip concatenation that also leave the next GroupNorm's statistics
+# ---------------------------------------------------------------------------------------------
+
+# GD_NN_JOINS=0: the torch ops (aten add / cat); A/B timing in tools/, never set in tests
+_JOINS = os.environ.get("GD_NN_JOINS", "1") != "0"
+# GD_NN_JOIN_STATS=1: a join also hands the GroupNorm that consumes it its statistics (partial sums + finish instead of the
+# statistics pass).  OFF by default: on the 8-view step it replaces 2 of 20 statistics passes (-0.04 ms of 44.5, inside the
+# run-to-run spread), and the last-bit difference of those means / rstds makes the step's outputs leave the previous
+# build's bits (profiles/unet_joins_ab.txt) -- without it the joins and the shared prefix reproduce them exactly
+_JOIN_STATS = os.environ.get("GD_NN_JOIN_STATS", "0") == "1"
+
+
+def join_supported(a, b) -> bool:
+    """Own join kernels: bf16 channels_last GPU tensors of one spatial size without autograd, channel counts that are
+    multiples of 8 (at most 2560 after the join), and ``b`` holding the same images as ``a`` or a divisor of them (b is
+    then read at image ``n % b.shape[0]``: the operand shared by the replicas of a guidance batch)."""
+    return (_JOINS and not torch.is_grad_enabled() and _is_nhwc_bf16(a) and _is_nhwc_bf16(b) and a.device == b.device
+            and a.shape[2:] == b.shape[2:] and a.shape[1] % 8 == 0 and b.shape[1] % 8 == 0 and 0 < b.shape[0] <= a.shape[0]
+            and a.shape[0] % b.shape[0] == 0 and a.shape[0] <= 65535 and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0)
+
+
+def _join_wants_stats(N, HW, Cc, next_norm) -> bool:
+    """The consumer is a GroupNorm that would run its own statistics pass (the two-pass form; the one-launch form has
+    none to save) and whose groups are whole 4-channel quads (what gd_nn_groupnorm_finish_partials adds up)."""
+    if next_norm is None or not _JOIN_STATS or not _EPILOGUE_STATS or next_norm.num_channels != Cc:
+        return False
+    G = next_norm.num_groups
+    if Cc % G or (Cc // G) % 4:
+        return False
+    return not (_GN_FUSED_SMALL and lib().gd_nn_groupnorm_silu_fused_supported(N, HW, Cc, G))
+
+
+def _join(a, b, concat: bool, next_norm, stats=None):
+    """``stats``: None = by the routing rule (_join_wants_stats); True = whenever ``next_norm``'s groups are whole quads (tests
+    and tools: the partial sums at any shape, whatever the switch says)."""
+    N, C0, H, W = a.shape
+    C1 = b.shape[1]
+    Cc = C0 + C1 if concat else C0
+    L = lib()
+    out = torch.empty((N, Cc, H, W), dtype=torch.bfloat16, device=a.device, memory_format=torch.channels_last)
+    if stats is None:
+        stats = _join_wants_stats(N, H * W, Cc, next_norm)
+    elif stats:
+        G = next_norm.num_groups if next_norm is not None else 0
+        stats = G > 0 and next_norm.num_channels == Cc and Cc % G == 0 and (Cc // G) % 4 == 0
+    rows = L.gd_nn_join_stat_rows(N, H * W, Cc) if stats else 0
+    part = torch.empty(N * (Cc // 4) * rows * 2, dtype=torch.float32, device=a.device) if rows else None
+    with torch.cuda.device(a.device):
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        part_p = None if part is None else part.data_ptr()
+        if concat:
+            ret = L.gd_nn_concat_gn_partials(stream, a.data_ptr(), b.data_ptr(), out.data_ptr(), part_p, N, b.shape[0], H * W,
+                                             C0, C1)
+        else:
+            ret = L.gd_nn_add_gn_partials(stream, a.data_ptr(), b.data_ptr(), out.data_ptr(), part_p, N, b.shape[0], H * W, C0)
+        _check(ret, "gd_nn_concat_gn_partials" if concat else "gd_nn_add_gn_partials", "gd_nn_elementwise_last_error")
+        if part is not None:
+            G, eps = next_norm.num_groups, next_norm.eps
+            mr = torch.empty(N * G * 2, dtype=torch.float32, device=a.device)
+            _check(L.gd_nn_groupnorm_finish_partials(stream, part.data_ptr(), N, rows, Cc, G, H * W, float(eps), mr.data_ptr()),
+                   "gd_nn_groupnorm_finish_partials")
+            out._gd_gn_stats = (mr, G, eps, out._version)
+    return out
+
+
+def _shared_images(b, n: int):
+    """``b`` repeated to ``n`` images (image i = b[i % len(b)]): the torch form of the join kernels' sharing rule."""
+    return b if b.shape[0] == n else b.repeat(n // b.shape[0], *([1] * (b.dim() - 1)))
+
+
+def add_join(a, b, next_norm=None):
+    """``a + b`` of two NHWC activations (``b`` may hold a divisor of a's images, see ``join_supported``).  ``next_norm``:
+    the GroupNorm module that consumes the sum, if the caller knows it -- under GD_NN_JOIN_STATS=1, where that GroupNorm
+    would run a statistics pass, the add leaves its partial sums and the finished ``mean_rstd`` rides on the result
+    (``gn_stats_of``)."""
+    # two operands of one batch and no statistics wanted: aten's add is already at copy rate (own kernel 0.93-1.02x on the
+    # step's shapes, profiles/unet_joins_kernel_times.txt) and stays; the own kernel reads a shared b without a repeated copy
+    if join_supported(a, b) and a.shape[1] == b.shape[1] and \
+            (b.shape[0] != a.shape[0] or _join_wants_stats(a.shape[0], a.shape[2] * a.shape[3], a.shape[1], next_norm)):
+        return _join(a, b, False, next_norm)
+    return a + _shared_images(b, a.shape[0])
+
+
+def concat_join(a, b, next_norm=None):
+    """``torch.cat([a, b], dim=1)`` likewise."""
+    if join_supported(a, b) and a.shape[1] + b.shape[1] <= 2560:
+        return _join(a, b, True, next_norm)
+    return torch.cat([a, _shared_images(b, a.shape[0])], dim=1)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -430,6 +541,27 @@ class route_batch:
     def __enter__(self):
         global _ROUTE_BATCH
         self.prev, _ROUTE_BATCH = _ROUTE_BATCH, self.value
+        return self
+
+    def __exit__(self, *exc):
+        global _ROUTE_BATCH
+        _ROUTE_BATCH = self.prev
+        return False
+
+
+class route_batch_shared:
+    """``with route_batch_shared(reps):`` -- inside, the call runs on ONE of the `reps` identical copies that the enclosing
+    ``route_batch(groups, samples)`` announced (the shared prefix of a guidance UNet call): groups / reps copies, samples /
+    reps entries.  A no-op without an enclosing route_batch or when the counts do not divide."""
+
+    def __init__(self, reps: int):
+        self.reps = int(reps)
+
+    def __enter__(self):
+        global _ROUTE_BATCH
+        self.prev = _ROUTE_BATCH
+        if self.prev is not None and self.reps > 1 and self.prev[0] % self.reps == 0 and self.prev[1] % self.reps == 0:
+            _ROUTE_BATCH = (self.prev[0] // self.reps, self.prev[1] // self.reps)
         return self
 
     def __exit__(self, *exc):
@@ -1388,14 +1520,19 @@ def _add_ln_fwd(x, residual, weight, bias, eps, want_sum):
     x = x.contiguous()
     if residual is not None:
         residual = residual.contiguous()
-    s = torch.empty_like(x) if (residual is not None and want_sum) else None
-    y = torch.empty_like(x)
+    like = x if residual is None else residual      # (x may hold a divisor of the residual's rows: read at row % x_rows)
+    s = torch.empty_like(like) if (residual is not None and want_sum) else None
+    y = torch.empty_like(like)
     L = lib()
     with torch.cuda.device(x.device):
-        ret = L.gd_nn_add_layernorm_forward(
-            torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-            None if residual is None else residual.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-            float(eps), None if s is None else s.data_ptr(), y.data_ptr(), x.numel() // Cc, Cc)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        res_p, s_p = None if residual is None else residual.data_ptr(), None if s is None else s.data_ptr()
+        if like.numel() == x.numel():
+            ret = L.gd_nn_add_layernorm_forward(stream, x.data_ptr(), res_p, weight.data_ptr(), bias.data_ptr(), float(eps), s_p,
+                                                y.data_ptr(), x.numel() // Cc, Cc)
+        else:
+            ret = L.gd_nn_add_layernorm_forward_bcast(stream, x.data_ptr(), res_p, weight.data_ptr(), bias.data_ptr(), float(eps),
+                                                      s_p, y.data_ptr(), like.numel() // Cc, Cc, x.numel() // Cc)
     if ret < 0:
         raise RuntimeError(f"gd_nn_add_layernorm_forward failed ({ret}): {L.gd_nn_elementwise_last_error().decode()}")
     return (x if residual is None else s), y
@@ -1434,8 +1571,11 @@ def add_layer_norm(x, residual, norm, want_sum: bool = True):
     Cc = x.shape[-1]
     ok = Cc % 8 == 0 and Cc <= 2048 and norm.weight.dtype == torch.bfloat16 and x.is_cuda and x.dtype == torch.bfloat16 and \
         (residual is None or (residual.is_cuda and residual.dtype == torch.bfloat16))
-    if ok and _rowwise_ok(x, residual, norm.weight, norm.bias):
+    shared = residual is not None and x.shape[0] != residual.shape[0]    # x: the residual stream shared by the batch's replicas
+    if ok and _rowwise_ok(x, residual, norm.weight, norm.bias) and (not shared or want_sum):
         return _add_ln_fwd(x, residual, norm.weight, norm.bias, norm.eps, want_sum)
+    if shared:
+        x = _shared_images(x, residual.shape[0])
     if ok and _ROW_TRAIN and torch.is_grad_enabled() and not norm.weight.requires_grad and not norm.bias.requires_grad:
         if residual is None:
             return x, _AddLayerNormTrain.apply(x, None, norm.weight, norm.bias, float(norm.eps))
@@ -1565,19 +1705,23 @@ def attention_d64_vt(q, k, vt):
 def attention_d64_vt_strided(q, k, vt, kv_len: int):
     """Cross-attention with V^T handed in as a [B, H*64, Skv] VIEW (rows contiguous, any batch stride: a channel slice of
     the all-layers context projection), ``kv_len`` <= Skv live keys (the rest of every V^T row is zero).  q: [B, S, H, 64],
-    k: [B, kv_len, H, 64] views."""
-    B, S, H, _ = q.shape
-    Skv = vt.shape[2]
-    assert vt.shape[:2] == (B, H * 64) and vt.stride(2) == 1 and vt.stride(1) == Skv and vt.dtype == torch.bfloat16 and Skv % 64 == 0
+    k: [B, kv_len, H, 64] views.  q may hold a divisor Bq of the B context entries -- the query shared by the replicas of a
+    guidance batch: entry b attends with q[b % Bq], one launch per replica on the same query rows (no repeated q exists)."""
+    Bq, S, H, _ = q.shape
+    B, Skv = vt.shape[0], vt.shape[2]
+    assert vt.shape[1] == H * 64 and vt.stride(2) == 1 and vt.stride(1) == Skv and vt.dtype == torch.bfloat16 and Skv % 64 == 0
+    assert k.shape[0] == B and B % Bq == 0
     L = lib()
     o = torch.empty((B, S, H * 64), dtype=torch.bfloat16, device=q.device)
     with torch.cuda.device(q.device):
-        ret = L.gd_nn_attention_d64_forward_vt_strided(torch.cuda.current_stream(q.device).cuda_stream, q.data_ptr(), k.data_ptr(),
-                                                       vt.data_ptr(), o.data_ptr(), B, S, Skv, H, q.stride(0), q.stride(1),
-                                                       k.stride(0), k.stride(1), vt.stride(0), o.stride(0), o.stride(1),
-                                                       64 ** -0.5, int(kv_len))
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_attention_d64_forward_vt_strided failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+        for r in range(0, B, Bq):
+            ret = L.gd_nn_attention_d64_forward_vt_strided(stream, q.data_ptr(), k[r:r + Bq].data_ptr(), vt[r:r + Bq].data_ptr(),
+                                                           o[r:r + Bq].data_ptr(), Bq, S, Skv, H, q.stride(0), q.stride(1),
+                                                           k.stride(0), k.stride(1), vt.stride(0), o.stride(0), o.stride(1),
+                                                           64 ** -0.5, int(kv_len))
+            if ret < 0:
+                raise RuntimeError(f"gd_nn_attention_d64_forward_vt_strided failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
     return o
 
 

@@ -284,6 +284,31 @@ int gd_nn_layernorm_backward(void* stream, const void* s, const void* dy, const 
  * ``norm(x)`` (one wave per row, fp32 statistics).  Inference only. */
 int gd_nn_add_layernorm_forward(void* stream, const void* x, const void* residual, const void* weight, const void* bias,
                                 float eps, void* sum_out, void* y, int64_t rows, int C);
+/* The same pass with x shared by the replicas of a batch: x holds x_rows rows (x_rows divides rows) and row r reads
+ * x[r % x_rows]; residual, sum_out and y have `rows` rows.  The shared prefix of a classifier-free-guidance UNet call
+ * (sd21.UNet2DConditionModel.forward(shared_reps=)) keeps its residual stream at one copy until the cross-attention, and
+ * this is the add that meets the per-replica attention output. */
+int gd_nn_add_layernorm_forward_bcast(void* stream, const void* x, const void* residual, const void* weight,
+                                      const void* bias, float eps, void* sum_out, void* y, int64_t rows, int C,
+                                      int64_t x_rows);
+
+/* Joins of the no-grad UNet with the GroupNorm partial sums of their result (diffusers Transformer2DModel's
+ * ``output = hidden_states + residual`` and CrossAttnUpBlock2D / UpBlock2D's ``torch.cat([hidden_states, res], dim=1)``,
+ * reached from Garment_3DGS/threestudio/models/guidance/stable_diffusion_guidance.py:153-157).  bf16 NHWC, 16-byte
+ * accesses, caller's stream.
+ *   gd_nn_add_gn_partials:     out[n][p][c] = a[n][p][c] + b[n % Nb][p][c]   (fp32 add of the two bf16 values, one
+ *                              rounding to nearest even: the bits of torch's bf16 add)
+ *   gd_nn_concat_gn_partials:  out[n][p][0:C0] = a[n][p][:],  out[n][p][C0:C0+C1] = b[n % Nb][p][:]
+ * a, out: N images of HW pixels; b: Nb images, Nb divides N (Nb == N: no sharing).  C (or C0 and C1) % 8 == 0,
+ * C0 + C1 <= 2560.  stat_part: NULL, or N * (C/4) * rows float2 with rows = gd_nn_join_stat_rows(N, HW, C) -- {sum, sum of
+ * squares} of the bf16 values stored, per 4-channel quad and pixel block, every element written by plain stores (no
+ * atomics, no zeroing; bit-reproducible), the layout gd_nn_groupnorm_finish_partials turns into mean_rstd when
+ * (C / G) % 4 == 0.  Errors: gd_nn_elementwise_last_error. */
+size_t gd_nn_join_stat_rows(int N, int HW, int C);
+int gd_nn_add_gn_partials(void* stream, const void* a, const void* b, void* out, float* stat_part, int N, int Nb, int HW,
+                          int C);
+int gd_nn_concat_gn_partials(void* stream, const void* a, const void* b, void* out, float* stat_part, int N, int Nb, int HW,
+                             int C0, int C1);
 
 /* Fused self-attention forward, head_dim 64, bf16, no mask (diffusers Attention -> scaled_dot_product_attention in
  * the UNet's spatial self-attention).  q, o: [B][S][H*64] with row stride q_rs / o_rs and batch stride q_bs / o_bs
