@@ -1245,12 +1245,40 @@ __global__ void conv3x3_flip_weights_kernel(const uint16_t* __restrict__ w, uint
     }
 }
 
-int g_first_grid = 2048;   // persistent workgroups of the first-conv kernel (GD_NN_FIRST_GRID overrides, tuning)
-int g_num_cus = 256;       // MI355X; refreshed from the device properties at the first patch launch
-int g_patch_persistent = -1;   // GD_NN_PATCH_PERSISTENT=0: one workgroup per tile (A/B)
 int g_route_scale = 1;     // kernel selection sees a batch of N * g_route_scale images (gd_nn_conv_set_route_scale)
 int g_force_split = -1;    // tuning hook: -1 heuristic, 1 = never split, S > 1 = force S ranges of the K-step sequence
 int g_force_variant = -1;  // tuning hook: 0 = 128x128, 1 = 128x256, 2 = 256x256, -1 = heuristic
+
+// The environment switches of the convolution family, read once at their first use.
+struct ConvEnv {
+    int split_px = 0;           // GD_NN_SPLIT_PX=128/256 forces the pixel extent of the split-K tile (A/B)
+    int multi_class = 1;        // GD_NN_CONV_MULTI=0: the classes back to back as before round 5 (same-box A/B)
+    int patch_persistent = 1;   // GD_NN_PATCH_PERSISTENT=0: one workgroup per tile (A/B)
+    int first_grid = 2048;      // persistent workgroups of the first-conv kernel (GD_NN_FIRST_GRID overrides, tuning)
+};
+const ConvEnv& conv_env()
+{
+    static const ConvEnv env = [] {
+        ConvEnv v;
+        if (const char* e = getenv("GD_NN_SPLIT_PX")) v.split_px = atoi(e);
+        if (const char* e = getenv("GD_NN_CONV_MULTI")) v.multi_class = atoi(e);
+        if (const char* e = getenv("GD_NN_PATCH_PERSISTENT")) v.patch_persistent = atoi(e) != 0;
+        if (const char* e = getenv("GD_NN_FIRST_GRID")) v.first_grid = atoi(e) > 0 ? atoi(e) : v.first_grid;
+        return v;
+    }();
+    return env;
+}
+
+// CUs of the chip (256: MI355X), from the device properties at the first patch launch: the first device that asks
+// answers for all (one value per process as before; the devices of a node are alike)
+int num_cus(int dev)
+{
+    static const int cus = [dev] {
+        int c = 0;
+        return hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && c > 0 ? c : 256;
+    }();
+    return cus;
+}
 
 // optional event timing of the conv kernel (bench.py's roofline line)
 struct ConvProf {
@@ -1269,6 +1297,84 @@ struct ConvProf {
     }
 } g_cprof;
 
+// One record of the profile = one entry call: opened before its launches (a split-K launch with its reduce, the four
+// classes of a multi launch), closed after them with the call's ALGORITHMIC flops and HBM bytes.
+struct ProfScope {
+    hipStream_t s;
+    hipEvent_t a = nullptr, b = nullptr;
+    ProfScope(const ProfScope&) = delete;      // owns its events until close() or the destructor
+    ProfScope& operator=(const ProfScope&) = delete;
+    explicit ProfScope(hipStream_t stream) : s(stream)
+    {
+        if (!g_cprof.on) return;
+        std::lock_guard<std::mutex> lk(g_cprof.mu);
+        a = g_cprof.get(); b = g_cprof.get();
+        if (a && b) (void)hipEventRecord(a, s);
+    }
+    void close(double flops, double bytes)
+    {
+        if (!a || !b) return;
+        (void)hipEventRecord(b, s);
+        std::lock_guard<std::mutex> lk(g_cprof.mu);
+        g_cprof.pending.push_back({a, b});
+        g_cprof.total_flops += flops;
+        g_cprof.total_bytes += bytes;
+        a = b = nullptr;
+    }
+    ~ProfScope()      // left without close() (an error return, or only one event was to be had): the events go back
+    {
+        if (!a && !b) return;
+        std::lock_guard<std::mutex> lk(g_cprof.mu);
+        if (a) g_cprof.pool.push_back(a);
+        if (b) g_cprof.pool.push_back(b);
+    }
+    // A stride-1 nine-tap layer of M pixels, direct form whatever the kernel multiplies (Winograd): every input element
+    // once, the taps' weights once, every output element once (and the residual, if any)
+    void close_s1(int64_t M, int Cin, int Cout, bool residual)
+    {
+        close(2.0 * (double)M * Cout * 9.0 * Cin,
+              2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout + (residual ? (double)M * Cout : 0.0)));
+    }
+};
+
+// The patch-staged, Winograd and wide-tile kernels take one argument list.  What differs per launch: the kernel `Kern`, its
+// LDS, the pixel tile (16 rows x `tile_w`), the channel slab `bn`, and whether the grid is persistent (plain patch kernel).
+struct TiledArgs {
+    void* stream;
+    const void* x;
+    const float* mean_rstd;
+    const void *gamma, *beta;
+    int groups, silu;
+    const void *w, *bias;
+    int bias_img_stride;
+    const void* residual;
+    void* y;
+    int N, H, W, Cin, Cout;
+    float* stat_part;
+};
+template <auto Kern>
+int launch_tiled(const TiledArgs& a, int lds, int tile_w, int bn, bool persistent)
+{
+    const int dev = current_device();
+    if (dev < 0) return dev;
+    if (const int r = reserve_lds<Kern>(dev, lds)) return r;
+    hipStream_t s = (hipStream_t)a.stream;
+    const int tiles_x = (a.W + tile_w - 1) / tile_w, tiles_y = (a.H + 15) / 16, tiles_n = (a.Cout + bn - 1) / bn;
+    const int nwg = a.N * tiles_x * tiles_y * tiles_n;
+    // persistent workgroups: one per CU (the LDS footprint allows no more), each walking tiles b, b + grid, ...; a
+    // multiple of 8 keeps the XCD-contiguous tile order.  Else one tile per workgroup (the persistent form of the Winograd
+    // kernel measured slower: nn_conv_wino.h)
+    int grid = nwg;
+    if (persistent && nwg > num_cus(dev)) grid = (nwg & 7) == 0 ? (num_cus(dev) & ~7) : num_cus(dev);
+    ProfScope prof(s);
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(512), lds, s, (const uint16_t*)a.x, (const uint16_t*)a.w,
+                       (const uint16_t*)a.bias, a.bias_img_stride, (const uint16_t*)a.residual, (uint16_t*)a.y, a.N, a.H,
+                       a.W, a.Cin, a.Cout, a.mean_rstd, (const uint16_t*)a.gamma, (const uint16_t*)a.beta, a.groups, a.silu,
+                       tiles_n, tiles_x, tiles_y, nwg, a.stat_part);
+    prof.close_s1((int64_t)a.N * a.H * a.W, a.Cin, a.Cout, a.residual != nullptr);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1280,9 +1386,8 @@ const char* gd_nn_conv_last_error(void) { return g_err; }
 // are dealt to 3 or 9 workgroups per tile, fp32 partials are combined by conv_splitk_reduce_kernel.
 // tools/splitk_sweep.py on MI355X (UNet maps at batch 1 and 2): the best split gives ~420 workgroups in flight while
 // every workgroup keeps >= 7-8 K-steps; beyond 24 ranges the fp32 partial traffic costs more than the idle CUs.
-static int pick_split(int64_t M, int64_t tiles, int steps, int target = 420)
+static int pick_split(int64_t tiles, int steps, int target = 420)
 {
-    (void)M;
     int s = (int)((target + tiles / 2) / tiles);
     const int cap = steps * 2 / 15 < 24 ? steps * 2 / 15 : 24;
     if (s > cap) s = cap;
@@ -1300,12 +1405,10 @@ static size_t split_ws_bytes(int split, int64_t M, int Cout)
 // Pixel extent of the split-K tile: 256 (the 128-channel x 256-pixel / 8-wave tile) on the larger of the small maps -- a
 // layer whose whole filter bank is re-read once per pixel tile is bound by that traffic (1280 -> 1280 @ 8^2 x 16 latents:
 // 236 MB of weight reads in 51 us), and the longer tile halves it -- else 128.  GD_NN_SPLIT_PX=128/256 forces (A/B).
-int g_split_px = 0;
 static int split_tile_px(int64_t M, int Cout)
 {
-    static int env_read = 0;
-    if (!env_read) { if (const char* e = getenv("GD_NN_SPLIT_PX")) g_split_px = atoi(e); env_read = 1; }
-    if (g_split_px == 128 || g_split_px == 256) return g_split_px;
+    const int forced = conv_env().split_px;
+    if (forced == 128 || forced == 256) return forced;
     // profiles/r05_split_px_sweep.txt (UNet layers at 1 / 2 / 4 / 16 latents): the long tile wins from 1024 GEMM rows on when the
     // layer has >= 8 channel tiles (1280-wide: 1.03-1.15x), from 2048 rows on otherwise (640-wide: 1.0-1.06x); below, the
     // 128-pixel tile's finer split fills the chip better (up to 1.35x)
@@ -1335,16 +1438,21 @@ static int choose_split(int64_t M, int Cout, int ntaps, int Cin)
     const int64_t tiles = ((M + px - 1) / px) * ((Cout + 127) / 128);
     if (tiles >= 256 || Cout % 8 || steps < 8) return 1;
     // (the 8-wave 128 x 256 tile holds 96 KB of LDS: one workgroup per CU, so one wave of 256 workgroups is the target)
-    return pick_split(M, tiles, steps, px == 256 ? 256 : 420);
+    return pick_split(tiles, steps, px == 256 ? 256 : 420);
 }
 
-static int launch_conv(hipStream_t s, const void* x, const void* weight, const void* bias, int bias_img_stride,
-                       const void* residual, void* y, int N, ConvGeom g, int Cin, int Cout, void* ws = nullptr,
-                       size_t ws_bytes = 0)
+static void add_tap(ConvGeom& g, int dy, int dx, int widx)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
-    // taps -> how far the activation descriptor must reach back so every soffset is >= 0
+    g.ty4 |= (uint64_t)(dy + 8) << (4 * g.ntaps);
+    g.tx4 |= (uint64_t)(dx + 8) << (4 * g.ntaps);
+    g.w4 |= (uint64_t)widx << (4 * g.ntaps);
+    g.ntaps++;
+}
+
+// Completes a geometry for its launch: how far the activation descriptor must reach back so every tap's soffset is >= 0,
+// the default count of filter slots, the bound of the 32-bit buffer offsets.
+static int finalize_geom(ConvGeom& g, int N, int Cin, int Cout)
+{
     int minlin = 0;
     for (int t = 0; t < g.ntaps; t++) {
         const int dy = (int)((g.ty4 >> (4 * t)) & 15u) - 8, dx = (int)((g.tx4 >> (4 * t)) & 15u) - 8;
@@ -1354,12 +1462,46 @@ static int launch_conv(hipStream_t s, const void* x, const void* weight, const v
     if (g.wtaps == 0) g.wtaps = 9;
     if (((double)N * g.Hin * g.Win + g.back) * Cin * 2.0 >= 2147483648.0 || (double)Cout * 9.0 * Cin * 2.0 >= 2147483648.0)
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3: activation / weight tensor must be < 2 GiB (32-bit buffer offsets)");
+    return GD_NN_OK;
+}
+
+// Tile of an unsplit launch over M GEMM rows: the 256x256 / 8-wave tile (2) has twice the MFMA work per byte staged through
+// LDS.  Rules distilled from tools/conv_kernel_bench.py on MI355X: it wins whenever Cout fills it and there is most of a
+// wave of tiles for 256 CUs; 128 ch x 256 px (1) wins for long pixel dimensions with deep K or huge M; otherwise the
+// 128x128 / 4-wave tile (0, 2 workgroups per CU) hides latency best.
+static int tile_variant(int64_t M, int Cin, int Cout)
+{
+    const int64_t Ms = M * g_route_scale;
+    const int64_t t256 = ((Ms + 255) / 256) * ((Cout + 255) / 256);
+    const int64_t t128x256 = ((Ms + 255) / 256) * ((Cout + 127) / 128);
+    if (Cout % 256 == 0 && t256 >= 192) return 2;
+    return t128x256 >= 512 && (Cin >= 512 || Ms >= (1 << 20)) ? 1 : 0;
+}
+
+// The stride-1 nine-tap layer of gd_nn_conv3x3_forward / _forward_ws: their argument check, then the geometry
+static int s1_geom(ConvGeom& g, const void* x, const void* weight, const void* y, int N, int H, int W, int Cin, int Cout)
+{
+    if (!x || !weight || !y) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
+    if (N <= 0 || H <= 0 || W <= 0 || Cin % BK || Cout % 4 || Cin <= 0 || Cout <= 0)
+        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3: need Cin % 64 == 0 and Cout % 4 == 0");
+    g = ConvGeom{};
+    g.Hin = g.Hg = g.Hout = H;
+    g.Win = g.Wg = g.Wout = W;
+    g.sy = g.sx = g.osy = g.osx = 1;
+    for (int ky = 0; ky < 3; ky++)
+        for (int kx = 0; kx < 3; kx++) add_tap(g, ky - 1, kx - 1, ky * 3 + kx);
+    return GD_NN_OK;
+}
+
+static int launch_conv(hipStream_t s, const void* x, const void* weight, const void* bias, int bias_img_stride,
+                       const void* residual, void* y, int N, ConvGeom g, int Cin, int Cout, void* ws = nullptr,
+                       size_t ws_bytes = 0)
+{
+    const int dev = current_device();
+    if (dev < 0) return dev;
+    if (const int r = finalize_geom(g, N, Cin, Cout)) return r;
     const int64_t M = (int64_t)N * g.Hg * g.Wg;
     if (M <= 0) return GD_NN_OK;
-    // tile choice: the 256x256 / 8-wave tile has twice the MFMA work per byte staged through LDS;
-    // use it when Cout fills it and there are enough tiles for 256 CUs, else 128 channels x 256
-    // pixels, else the 128x128 / 4-wave tile.
-    const int64_t Mo = (int64_t)N * g.Hout * g.Wout;
     int split = ws ? choose_split(M, Cout, g.ntaps, Cin) : 1;
     if (split > 1 && ws_bytes < split_ws_bytes(split, M, Cout)) split = 1;
     float* partial = split > 1 ? (float*)ws : nullptr;
@@ -1369,33 +1511,14 @@ static int launch_conv(hipStream_t s, const void* x, const void* weight, const v
     const int spx = split > 1 ? split_tile_px(M, Cout) : 128;
     int variant = split > 1 ? (spx == 256 ? 1 : 0) : g_force_variant;
     if (variant < 0 && small_tile_nosplit(M, Cout, g.ntaps, Cin)) variant = 6;
-    if (variant < 0) {
-        // rules distilled from tools/conv_kernel_bench.py on MI355X: the 256x256 tile wins whenever Cout fills it
-        // and there is most of a wave of tiles; 128 ch x 256 px wins for long pixel dimensions with deep K or huge M;
-        // otherwise the 128x128 tile (2 workgroups per CU) hides latency best.
-        const int64_t Ms = M * g_route_scale;
-        const int64_t t256 = ((Ms + 255) / 256) * ((Cout + 255) / 256);
-        const int64_t t128x256 = ((Ms + 255) / 256) * ((Cout + 127) / 128);
-        if (Cout % 256 == 0 && t256 >= 192) variant = 2;
-        else if (Cout <= 32 && Ms >= (1 << 18)) variant = 4;   // few output channels (first conv's dgrad, Cout = 4)
-        else if (t128x256 >= 512 && (Cin >= 512 || Ms >= (1 << 20))) variant = 1;
-        else variant = 0;
-    }
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
+    if (variant < 0)   // few output channels (first conv's dgrad, Cout = 4), else the shared rule
+        variant = Cout <= 32 && M * g_route_scale >= (1 << 18) ? 4 : tile_variant(M, Cin, Cout);
+    ProfScope prof(s);
 #define GD_LAUNCH(BN_, BM_, WN_, WM_)                                                                              \
     do {                                                                                                           \
-        auto kern = conv3x3_nhwc_bf16_kernel<BN_, BM_, WN_, WM_>;                                                  \
+        constexpr auto kern = conv3x3_nhwc_bf16_kernel<BN_, BM_, WN_, WM_>;                                        \
         constexpr int lds = 2 * (BN_ + BM_) * BK * 2;                                                              \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);         \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
+        if (const int r = reserve_lds<kern>(dev, lds)) return r;                                                   \
         const int tiles_m = (int)((M + BM_ - 1) / BM_), tiles_n = (Cout + BN_ - 1) / BN_;                          \
         const int nwg = tiles_m * tiles_n;                                                                         \
         hipLaunchKernelGGL(kern, dim3(nwg, split), dim3(64 * WN_ * WM_), lds, s, (const uint16_t*)x,               \
@@ -1421,83 +1544,42 @@ static int launch_conv(hipStream_t s, const void* x, const void* weight, const v
                                tiles_n, M, Cout, g.Hg * g.Wg, g.Wg, g.Hout, g.Wout, g.osy, g.osx, g.ooy, g.oox,
                                (const uint16_t*)bias, bias_img_stride, (const uint16_t*)residual, (uint16_t*)y);
     }
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        g_cprof.total_flops += 2.0 * (double)M * Cout * (double)g.ntaps * Cin;
-        // algorithmic HBM bytes: every input element once, the taps' weights once, every output element once
-        g_cprof.total_bytes += 2.0 * ((double)N * g.Hin * g.Win * Cin + (double)g.ntaps * Cin * Cout + (double)M * Cout +
-                                      (residual ? (double)M * Cout : 0.0));
-    }
+    // algorithmic HBM bytes: every input element once, the taps' weights once, every output element once
+    prof.close(2.0 * (double)M * Cout * (double)g.ntaps * Cin,
+               2.0 * ((double)N * g.Hin * g.Win * Cin + (double)g.ntaps * Cin * Cout + (double)M * Cout +
+                      (residual ? (double)M * Cout : 0.0)));
     return launch_status();
-}
-
-static void add_tap(ConvGeom& g, int dy, int dx, int widx)
-{
-    g.ty4 |= (uint64_t)(dy + 8) << (4 * g.ntaps);
-    g.tx4 |= (uint64_t)(dx + 8) << (4 * g.ntaps);
-    g.w4 |= (uint64_t)widx << (4 * g.ntaps);
-    g.ntaps++;
 }
 
 // One launch for up to four geometries of the same layer (conv3x3_nhwc_bf16_multi_kernel).  Returns 1 if the classes were
 // launched, 0 if the shape wants split-K or differing tiles (the caller then launches the classes one by one), < 0 on error.
-int g_multi_class = 1;      // GD_NN_CONV_MULTI=0: the classes back to back as before round 5 (same-box A/B)
 static int launch_conv_multi(hipStream_t s, const void* x, const void* const* weights, const void* bias, int bias_img_stride,
                              const void* residual, void* y, int N, ConvGeom* geoms, int ncls, int Cin, int Cout, bool may_split)
 {
-    static int env_read = 0;
-    if (!env_read) { if (const char* e = getenv("GD_NN_CONV_MULTI")) g_multi_class = atoi(e); env_read = 1; }
-    if (!g_multi_class || ncls < 2 || ncls > 4 || g_force_variant >= 0 || g_force_split >= 0) return 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
-    int64_t Mmax = 0, Msum = 0;
+    if (!conv_env().multi_class || ncls < 2 || ncls > 4 || g_force_variant >= 0 || g_force_split >= 0) return 0;
+    const int dev = current_device();
+    if (dev < 0) return dev;
+    int64_t Msum = 0;
     double flops = 0, bytes = 0;
     for (int c = 0; c < ncls; c++) {
         ConvGeom& g = geoms[c];
-        int minlin = 0;
-        for (int t = 0; t < g.ntaps; t++) {
-            const int dy = (int)((g.ty4 >> (4 * t)) & 15u) - 8, dx = (int)((g.tx4 >> (4 * t)) & 15u) - 8;
-            minlin = dy * g.Win + dx < minlin ? dy * g.Win + dx : minlin;
-        }
-        g.back = -minlin;
-        if (g.wtaps == 0) g.wtaps = 9;
-        if (((double)N * g.Hin * g.Win + g.back) * Cin * 2.0 >= 2147483648.0 || (double)Cout * 9.0 * Cin * 2.0 >= 2147483648.0)
-            return fail(GD_NN_ERR_INVALID_ARG, "conv3x3: activation / weight tensor must be < 2 GiB (32-bit buffer offsets)");
+        if (const int r = finalize_geom(g, N, Cin, Cout)) return r;
         const int64_t M = (int64_t)N * g.Hg * g.Wg;
         if (M <= 0) return 0;
         if (may_split && choose_split(M, Cout, g.ntaps, Cin) > 1) return 0;     // small maps: the split-K path, class by class
-        Mmax = M > Mmax ? M : Mmax;
         Msum += M;
         flops += 2.0 * (double)M * Cout * (double)g.ntaps * Cin;
         bytes += 2.0 * ((double)g.ntaps * Cin * Cout + (double)M * Cout + (residual ? (double)M * Cout : 0.0));
     }
-    bytes += 2.0 * (double)N * geoms[0].Hin * geoms[0].Win * Cin;
-    // tile choice on the SUM of the classes' rows (they run concurrently), same rules as launch_conv
-    int variant = 0;
-    {
-        const int64_t Ms = Msum * g_route_scale;
-        const int64_t t256 = ((Ms + 255) / 256) * ((Cout + 255) / 256);
-        const int64_t t128x256 = ((Ms + 255) / 256) * ((Cout + 127) / 128);
-        if (Cout % 256 == 0 && t256 >= 192) variant = 2;
-        else if (t128x256 >= 512 && (Cin >= 512 || Ms >= (1 << 20))) variant = 1;
-    }
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
+    bytes += 2.0 * (double)N * geoms[0].Hin * geoms[0].Win * Cin;     // the classes share the input: counted once
+    // tile choice on the SUM of the classes' rows (they run concurrently), same rule as launch_conv
+    const int variant = tile_variant(Msum, Cin, Cout);
+    ProfScope prof(s);
 #define GD_LAUNCH_M(BN_, BM_, WN_, WM_)                                                                            \
     do {                                                                                                           \
-        auto kern = conv3x3_nhwc_bf16_multi_kernel<BN_, BM_, WN_, WM_>;                                            \
+        constexpr auto kern = conv3x3_nhwc_bf16_multi_kernel<BN_, BM_, WN_, WM_>;                                  \
         constexpr int lds = 2 * (BN_ + BM_) * BK * 2;                                                              \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);         \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
+        if (const int r = reserve_lds<kern>(dev, lds)) return r;                                                   \
         ConvGeomSet gs = {};                                                                                       \
         gs.n = ncls;                                                                                               \
         const int tiles_n = (Cout + BN_ - 1) / BN_;                                                                \
@@ -1519,24 +1601,37 @@ static int launch_conv_multi(hipStream_t s, const void* x, const void* const* we
     else if (variant == 1) GD_LAUNCH_M(128, 256, 2, 4);
     else GD_LAUNCH_M(128, 128, 2, 2);
 #undef GD_LAUNCH_M
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        g_cprof.total_flops += flops;
-        g_cprof.total_bytes += bytes;
-    }
-    (void)Mmax;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return 1;
+    prof.close(flops, bytes);
+    const int r = launch_status();
+    return r < 0 ? r : 1;
 }
-
 
 static int launch_patch(void* stream, const void* x, const float* mean_rstd, const void* gamma, const void* beta,
                         int groups, int apply_silu, const void* weight, const void* bias, int bias_img_stride,
                         const void* residual, void* y, int N, int H, int W, int Cin, int Cout,
-                        float* stat_part = nullptr);
+                        float* stat_part = nullptr)
+{
+    if (!x || !weight || !y) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
+    if (N <= 0 || H <= 0 || W <= 0 || Cin % BK || Cout % 4 || Cin <= 0 || Cout <= 0)
+        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_gn: need Cin % 64 == 0 and Cout % 4 == 0");
+    if (mean_rstd && (!gamma || !beta || groups <= 0 || Cin % groups))
+        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_gn: GroupNorm needs gamma, beta and Cin % groups == 0");
+    if ((double)N * H * W * Cin * 2.0 >= 2147483648.0 || (double)Cout * 9.0 * Cin * 2.0 >= 2147483648.0)
+        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_gn: activation / weight tensor must be < 2 GiB (32-bit buffer offsets)");
+    const TiledArgs a = {stream, x, mean_rstd, gamma, beta, groups, apply_silu, weight, bias, bias_img_stride, residual, y,
+                         N, H, W, Cin, Cout, stat_part};
+    int bn = (Cout % 256 == 0) ? 256 : 128;
+    if (g_force_variant == 1 || g_force_variant == 0) bn = 128;
+    if (g_force_variant == 2) bn = 256;
+    const bool persistent = conv_env().patch_persistent != 0;      // the plain kernel only
+    constexpr auto lds = [](int slab) { return 2 * (kPatchPix + 4) * BK * 2 + 2 * slab * BK * 2; };
+    if (bn == 256)
+        return mean_rstd ? launch_tiled<conv3x3_gn_patch_kernel<256, 2, 4, true>>(a, lds(256), 16, 256, false)
+                         : launch_tiled<conv3x3_patch_stream_kernel<256, 2, 4, false>>(a, lds(256), 16, 256, persistent);
+    return mean_rstd ? launch_tiled<conv3x3_gn_patch_kernel<128, 2, 4, true>>(a, lds(128), 16, 128, false)
+                     : launch_tiled<conv3x3_patch_stream_kernel<128, 2, 4, false>>(a, lds(128), 16, 128, persistent);
+}
+
 
 // Plain stride-1 convolutions run on the persistent patch-staged kernel (LDS-DMA patch) once its (image, 16x16
 // patch, 128- or 256-channel slab) grid has >= 256 workgroups: 1.08-1.24x faster than the implicit-GEMM tiles on
@@ -1578,105 +1673,21 @@ int gd_nn_conv3x3_forward_ws(void* stream, const void* x, const void* weight, co
                              const void* residual, void* y, int N, int H, int W, int Cin, int Cout, void* ws,
                              size_t ws_bytes)
 {
-    if (!x || !weight || !y) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || Cin % BK || Cout % 4 || Cin <= 0 || Cout <= 0)
-        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3: need Cin % 64 == 0 and Cout % 4 == 0");
+    ConvGeom g;
+    if (const int r = s1_geom(g, x, weight, y, N, H, W, Cin, Cout)) return r;
     if (prefer_patch(N, H, W, Cout))
         return launch_patch(stream, x, nullptr, nullptr, nullptr, 0, 0, weight, bias, bias_img_stride, residual, y, N, H, W,
                             Cin, Cout);
-    ConvGeom g = {};
-    g.Hin = g.Hg = g.Hout = H;
-    g.Win = g.Wg = g.Wout = W;
-    g.sy = g.sx = g.osy = g.osx = 1;
-    for (int ky = 0; ky < 3; ky++)
-        for (int kx = 0; kx < 3; kx++) add_tap(g, ky - 1, kx - 1, ky * 3 + kx);
     return launch_conv((hipStream_t)stream, x, weight, bias, bias_img_stride, residual, y, N, g, Cin, Cout, ws, ws_bytes);
 }
 
+// (never the patch kernel, unlike _forward_ws: callers rely on that difference for the scratch query)
 int gd_nn_conv3x3_forward(void* stream, const void* x, const void* weight, const void* bias, int bias_img_stride,
                           const void* residual, void* y, int N, int H, int W, int Cin, int Cout)
 {
-    if (!x || !weight || !y) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || Cin % BK || Cout % 4 || Cin <= 0 || Cout <= 0)
-        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3: need Cin % 64 == 0 and Cout % 4 == 0");
-    ConvGeom g = {};
-    g.Hin = g.Hg = g.Hout = H;
-    g.Win = g.Wg = g.Wout = W;
-    g.sy = g.sx = g.osy = g.osx = 1;
-    for (int ky = 0; ky < 3; ky++)
-        for (int kx = 0; kx < 3; kx++) add_tap(g, ky - 1, kx - 1, ky * 3 + kx);
+    ConvGeom g;
+    if (const int r = s1_geom(g, x, weight, y, N, H, W, Cin, Cout)) return r;
     return launch_conv((hipStream_t)stream, x, weight, bias, bias_img_stride, residual, y, N, g, Cin, Cout);
-}
-
-static int launch_patch(void* stream, const void* x, const float* mean_rstd, const void* gamma, const void* beta,
-                        int groups, int apply_silu, const void* weight, const void* bias, int bias_img_stride,
-                        const void* residual, void* y, int N, int H, int W, int Cin, int Cout,
-                        float* stat_part)
-{
-    if (!x || !weight || !y) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
-    if (N <= 0 || H <= 0 || W <= 0 || Cin % BK || Cout % 4 || Cin <= 0 || Cout <= 0)
-        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_gn: need Cin % 64 == 0 and Cout % 4 == 0");
-    if (mean_rstd && (!gamma || !beta || groups <= 0 || Cin % groups))
-        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_gn: GroupNorm needs gamma, beta and Cin % groups == 0");
-    if ((double)N * H * W * Cin * 2.0 >= 2147483648.0 || (double)Cout * 9.0 * Cin * 2.0 >= 2147483648.0)
-        return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_gn: activation / weight tensor must be < 2 GiB (32-bit buffer offsets)");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
-    if (g_patch_persistent < 0) {
-        const char* e = getenv("GD_NN_PATCH_PERSISTENT");
-        g_patch_persistent = (e && atoi(e) == 0) ? 0 : 1;
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) g_num_cus = cus;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
-    const int64_t M = (int64_t)N * H * W;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
-#define GD_LAUNCH_P(BN_, GN_)                                                                                         \
-    do {                                                                                                           \
-        auto kern = GN_ ? conv3x3_gn_patch_kernel<BN_, 2, 4, true> : conv3x3_patch_stream_kernel<BN_, 2, 4, false>; \
-        constexpr int lds = 2 * (kPatchPix + 4) * BK * 2 + 2 * BN_ * BK * 2;                                       \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);         \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
-        const int tiles_n = (Cout + BN_ - 1) / BN_;                                                                \
-        const int nwg = N * tiles_x * tiles_y * tiles_n;                                                           \
-        /* persistent workgroups: one per CU (the LDS footprint allows no more), each walking tiles b, b + grid, */ \
-        /* ...; a multiple of 8 keeps the XCD-contiguous tile order */                                             \
-        int grid = nwg;                                                                                            \
-        if (g_patch_persistent && !(GN_) && nwg > g_num_cus) grid = (nwg & 7) == 0 ? (g_num_cus & ~7) : g_num_cus; \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, (const uint16_t*)x, (const uint16_t*)weight,       \
-                           (const uint16_t*)bias, bias_img_stride, (const uint16_t*)residual, (uint16_t*)y, N, H,  \
-                           W, Cin, Cout, mean_rstd, (const uint16_t*)gamma, (const uint16_t*)beta, groups,         \
-                           apply_silu, tiles_n, tiles_x, tiles_y, nwg, stat_part);                                 \
-    } while (0)
-    int bn = (Cout % 256 == 0) ? 256 : 128;
-    if (g_force_variant == 1 || g_force_variant == 0) bn = 128;
-    if (g_force_variant == 2) bn = 256;
-    if (mean_rstd) {
-        if (bn == 256) GD_LAUNCH_P(256, true);
-        else GD_LAUNCH_P(128, true);
-    } else {
-        if (bn == 256) GD_LAUNCH_P(256, false);
-        else GD_LAUNCH_P(128, false);
-    }
-#undef GD_LAUNCH_P
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        g_cprof.total_flops += 2.0 * (double)M * Cout * 9.0 * Cin;
-        g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
-                                      (residual ? (double)M * Cout : 0.0));
-    }
-    return launch_status();
 }
 
 int gd_nn_conv3x3_gn_forward(void* stream, const void* x, const float* mean_rstd, const void* gamma, const void* beta,
@@ -1750,46 +1761,10 @@ static int launch_wino(void* stream, const void* x, const float* mean_rstd, cons
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_wino: need Cin % 32 == 0, Cout % 8 == 0, Cout >= 64, H, W >= 16, tensors < 2 GiB");
     if (mean_rstd && (!gamma || !beta || groups <= 0 || Cin % groups))
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_wino: GroupNorm needs gamma, beta and Cin % groups == 0");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16;
-    const int64_t M = (int64_t)N * H * W;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
-    const int tiles_n = (Cout + 127) / 128;
-    const int nwg = N * tiles_x * tiles_y * tiles_n;
-    const int grid = nwg;      // one tile per workgroup (the persistent form measured slower: nn_conv_wino.h)
-#define GD_LAUNCH_W(GN_)                                                                                           \
-    do {                                                                                                           \
-        auto kern = conv3x3_wino_kernel<GN_>;                                                                      \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kWinoLds);    \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), kWinoLds, s, (const uint16_t*)x, (const uint16_t*)u,       \
-                           (const uint16_t*)bias, bias_img_stride, (const uint16_t*)residual, (uint16_t*)y, N, H,  \
-                           W, Cin, Cout, mean_rstd, (const uint16_t*)gamma, (const uint16_t*)beta, groups,         \
-                           apply_silu, tiles_n, tiles_x, tiles_y, nwg, stat_part);                                 \
-    } while (0)
-    if (mean_rstd) GD_LAUNCH_W(true);
-    else GD_LAUNCH_W(false);
-#undef GD_LAUNCH_W
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        // ALGORITHMIC flops of the convolution (direct form), whatever the kernel multiplies
-        g_cprof.total_flops += 2.0 * (double)M * Cout * 9.0 * Cin;
-        g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
-                                      (residual ? (double)M * Cout : 0.0));
-    }
-    return launch_status();
+    const TiledArgs a = {stream, x, mean_rstd, gamma, beta, groups, apply_silu, u, bias, bias_img_stride, residual, y,
+                         N, H, W, Cin, Cout, stat_part};
+    return mean_rstd ? launch_tiled<conv3x3_wino_kernel<true>>(a, kWinoLds, 16, 128, false)
+                     : launch_tiled<conv3x3_wino_kernel<false>>(a, kWinoLds, 16, 128, false);
 }
 
 int gd_nn_conv3x3_wino_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,
@@ -1846,44 +1821,10 @@ static int launch_wide(void* stream, const void* x, const float* mean_rstd, cons
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_wide: need Cin % 32 == 0, Cout % 8 == 0, Cout >= 64, H, W >= 16, tensors < 2 GiB");
     if (mean_rstd && (!gamma || !beta || groups <= 0 || Cin % groups))
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_wide: GroupNorm needs gamma, beta and Cin % groups == 0");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
-    hipStream_t s = (hipStream_t)stream;
-    const int tiles_x = (W + 31) / 32, tiles_y = (H + 15) / 16;
-    const int64_t M = (int64_t)N * H * W;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
-    const int tiles_n = (Cout + 127) / 128;
-    const int nwg = N * tiles_x * tiles_y * tiles_n;
-#define GD_LAUNCH_WD(GN_)                                                                                          \
-    do {                                                                                                           \
-        auto kern = conv3x3_wide_kernel<GN_>;                                                                      \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kWideLds);    \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), kWideLds, s, (const uint16_t*)x, (const uint16_t*)u,        \
-                           (const uint16_t*)bias, bias_img_stride, (const uint16_t*)residual, (uint16_t*)y, N, H,  \
-                           W, Cin, Cout, mean_rstd, (const uint16_t*)gamma, (const uint16_t*)beta, groups,         \
-                           apply_silu, tiles_n, tiles_x, tiles_y, nwg, stat_part);                                 \
-    } while (0)
-    if (mean_rstd) GD_LAUNCH_WD(true);
-    else GD_LAUNCH_WD(false);
-#undef GD_LAUNCH_WD
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        g_cprof.total_flops += 2.0 * (double)M * Cout * 9.0 * Cin;
-        g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
-                                      (residual ? (double)M * Cout : 0.0));
-    }
-    return launch_status();
+    const TiledArgs a = {stream, x, mean_rstd, gamma, beta, groups, apply_silu, u, bias, bias_img_stride, residual, y,
+                         N, H, W, Cin, Cout, stat_part};
+    return mean_rstd ? launch_tiled<conv3x3_wide_kernel<true>>(a, kWideLds, 32, 128, false)
+                     : launch_tiled<conv3x3_wide_kernel<false>>(a, kWideLds, 32, 128, false);
 }
 
 int gd_nn_conv3x3_wide_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,
@@ -1923,22 +1864,6 @@ size_t gd_nn_conv3x3_first_stat_rows(int N, int H, int W, int Cin, int Cout)
 }
 
 static int first_forward(void* stream, const void* x, const void* weight, const void* bias, void* y, int N, int H, int W,
-                         int Cin, int Cout, float* stat_part);
-
-int gd_nn_conv3x3_first_forward(void* stream, const void* x, const void* weight, const void* bias, void* y, int N, int H,
-                                int W, int Cin, int Cout)
-{
-    return first_forward(stream, x, weight, bias, y, N, H, W, Cin, Cout, nullptr);
-}
-
-int gd_nn_conv3x3_first_forward_stats(void* stream, const void* x, const void* weight, const void* bias, void* y, int N,
-                                      int H, int W, int Cin, int Cout, float* stat_part)
-{
-    if (!stat_part) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_first_forward_stats: stat_part is NULL");
-    return first_forward(stream, x, weight, bias, y, N, H, W, Cin, Cout, stat_part);
-}
-
-static int first_forward(void* stream, const void* x, const void* weight, const void* bias, void* y, int N, int H, int W,
                          int Cin, int Cout, float* stat_part)
 {
     if (!x || !weight || !y) return fail(GD_NN_ERR_INVALID_ARG, "null pointer");
@@ -1964,10 +1889,10 @@ static int first_forward(void* stream, const void* x, const void* weight, const 
     if (blocks > 2147483647LL) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_first: tensor too large");
     const size_t lds = (size_t)9 * Cin * Cout * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
+    const int first_grid = conv_env().first_grid;
     if (groups > 2147483647LL) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_first: tensor too large");
-    if (const char* e = getenv("GD_NN_FIRST_GRID")) g_first_grid = atoi(e) > 0 ? atoi(e) : g_first_grid;
 #define GD_FIRST(C_)                                                                                               \
-    hipLaunchKernelGGL(conv3x3_first_kernel<C_>, dim3((unsigned)(blocks < g_first_grid ? blocks : g_first_grid)), dim3(256), lds, s, (const uint16_t*)x,    \
+    hipLaunchKernelGGL(conv3x3_first_kernel<C_>, dim3((unsigned)(blocks < first_grid ? blocks : first_grid)), dim3(256), lds, s, (const uint16_t*)x,    \
                        (const uint16_t*)weight, (const uint16_t*)bias, (uint16_t*)y, N, H, W, Cout)
     if (Cin == 1) GD_FIRST(1);
     else if (Cin == 2) GD_FIRST(2);
@@ -1975,6 +1900,19 @@ static int first_forward(void* stream, const void* x, const void* weight, const 
     else GD_FIRST(4);
 #undef GD_FIRST
     return launch_status();
+}
+
+int gd_nn_conv3x3_first_forward(void* stream, const void* x, const void* weight, const void* bias, void* y, int N, int H,
+                                int W, int Cin, int Cout)
+{
+    return first_forward(stream, x, weight, bias, y, N, H, W, Cin, Cout, nullptr);
+}
+
+int gd_nn_conv3x3_first_forward_stats(void* stream, const void* x, const void* weight, const void* bias, void* y, int N,
+                                      int H, int W, int Cin, int Cout, float* stat_part)
+{
+    if (!stat_part) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_first_forward_stats: stat_part is NULL");
+    return first_forward(stream, x, weight, bias, y, N, H, W, Cin, Cout, stat_part);
 }
 
 static ConvGeom s2_forward_geom(int Hin, int Win, int pad_lo)

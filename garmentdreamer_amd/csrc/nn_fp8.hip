@@ -260,8 +260,8 @@ __global__ __launch_bounds__(256) void pack_weights_fp8_kernel(const uint16_t* _
 int launch(hipStream_t s, const void* x, const void* w, const void* bias, int bias_img_stride, const void* residual, void* y,
            int Nimg, TapGeom g, int Cin, int CinP, int Cout, float dq)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
+    const int dev = current_device();
+    if (dev < 0) return dev;
     int minlin = 0;
     for (int t = 0; t < g.ntaps; t++) {
         const int dy = (int)((g.ty4 >> (4 * t)) & 15u) - 8, dx = (int)((g.tx4 >> (4 * t)) & 15u) - 8;
@@ -279,13 +279,9 @@ int launch(hipStream_t s, const void* x, const void* w, const void* bias, int bi
     else if (t128x256 >= 512 && (CinP * g.ntaps >= 1024 || M >= (1 << 20))) variant = 1;
 #define GD_LAUNCH8(BN_, BM_, WN_, WM_)                                                                              \
     do {                                                                                                           \
-        auto kern = gemm_taps_fp8_kernel<BN_, BM_, WN_, WM_>;                                                      \
+        constexpr auto kern = gemm_taps_fp8_kernel<BN_, BM_, WN_, WM_>;                                            \
         constexpr int lds = 2 * (BN_ + BM_) * BKB;                                                                 \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);         \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
+        if (const int r = reserve_lds<kern>(dev, lds)) return r;                                                   \
         const int tiles_m = (int)((M + BM_ - 1) / BM_), tiles_n = (Cout + BN_ - 1) / BN_;                          \
         const int nwg = tiles_m * tiles_n;                                                                         \
         hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * WN_ * WM_), lds, s, (const uint8_t*)x, (const uint8_t*)w,    \

@@ -382,13 +382,10 @@ template <int MODE>
 int launch(void* stream, const void* x, const void* w, const void* bias, const void* residual, void* y, int64_t M, int K,
            int N, int ldy)
 {
-    static bool attr_set = false;
-    auto kfn = gemm256_kernel<MODE>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess)
-            return fail(GD_NN_ERR_HIP, "gd_nn_gemm: cannot reserve 160 KiB of LDS");
-        attr_set = true;
-    }
+    constexpr auto kfn = gemm256_kernel<MODE>;
+    const int dev = current_device();
+    if (dev < 0) return dev;
+    if (const int r = reserve_lds<kfn>(dev, kLds, "gd_nn_gemm: cannot reserve 160 KiB of LDS")) return r;
     const int ch_tile = MODE == kModeGeglu ? 128 : 256;
     const int tiles_n = (N + ch_tile - 1) / ch_tile;
     const int64_t tiles_m = (M + 255) / 256;

@@ -22,4 +22,28 @@ int launch_status(const char* msg = nullptr)
     return e == hipSuccess ? GD_NN_OK : fail(GD_NN_ERR_HIP, msg ? msg : hipGetErrorString(e));
 }
 
+// The current device, 0 .. kMaxDevices - 1 (the bound of the per-device tables of the library); on failure the error code
+// (< 0) with the message set.
+constexpr int kMaxDevices = 16;
+int current_device()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
+    return dev;
+}
+
+// Reserves `lds` bytes of dynamic LDS for kernel `Kern`, once per device: every launcher of the library keys it so.  The
+// key is the kernel INSTANTIATION, a non-type template argument -- all instantiations of one kernel template share their
+// function-pointer TYPE, so a helper templated on the type would take conv3x3_wino_kernel<false> for done after <true> ran.
+template <auto Kern>
+int reserve_lds(int dev, int lds, const char* msg = "cannot reserve the kernel's dynamic LDS")
+{
+    static bool done[kMaxDevices] = {false};
+    if (done[dev]) return GD_NN_OK;
+    if (hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return fail(GD_NN_ERR_HIP, msg);
+    done[dev] = true;
+    return GD_NN_OK;
+}
+
 }  // namespace

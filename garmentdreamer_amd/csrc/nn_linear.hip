@@ -211,13 +211,9 @@ template <bool GEGLU>
 int launch_k320(void* stream, const void* x, const void* weight, const void* bias, void* y, int64_t M, int nb)
 {
     static_assert((kStages & (kStages - 1)) == 0, "stage index by mask");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
-    static bool attr_set[16] = {false};
-    if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void*)linear_320_kernel<GEGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        attr_set[dev] = true;
-    }
+    const int dev = current_device();
+    if (dev < 0) return dev;
+    if (const int r = reserve_lds<linear_320_kernel<GEGLU>>(dev, kLds)) return r;
     const int ntiles = (int)((M + kBM - 1) / kBM);
     // 256 workgroups (one per CU of an MI355X; a multiple of 8 nb so that blockIdx -> (XCD, column block, tile slot) is
     // exact), fewer for short row sets

@@ -617,10 +617,8 @@ def _conv_route(N, H, W, Cin, Cout, gn=False):
 def _conv_launch(x, w_khwc, bias, residual, out_channels):
     N, Cin, H, W = x.shape
     route = _conv_route(N, H, W, Cin, out_channels)
-    if route == "wino":
-        return _wino_launch(x, w_khwc, bias, residual, out_channels)
-    if route == "wide":
-        return _wide_launch(x, w_khwc, bias, residual, out_channels)
+    if route is not None:
+        return _tiled_launch(route, x, w_khwc, bias, residual, out_channels)
     L = lib()
     y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device,
                     memory_format=torch.channels_last)
@@ -639,107 +637,75 @@ def _conv_launch(x, w_khwc, bias, residual, out_channels):
     return y
 
 
-def _patch_launch(x, w_khwc, bias, residual, out_channels):
-    """Plain 3x3/s1/p1 convolution on the patch-staged kernel (LDS-DMA patch, no GroupNorm)."""
+def _packed(weight, kind):
+    """Cached filter bank of a frozen conv weight (channels_last, i.e. [Cout][3][3][Cin] in memory -- also of a flipped
+    dgrad weight tensor) in the step images of a tiled kernel (include/gd_nn.h): kind "wino" = Winograd F(2,3), 32 KB
+    each; "wide" = the wide-tile kernel's re-packing, 24 KB each."""
+    attr = "_gd_" + kind
+    u = getattr(weight, attr, None)
+    key = (weight.data_ptr(), weight._version)
+    if u is None or u.device != weight.device or getattr(weight, attr + "_key", None) != key:
+        L, name = lib(), f"gd_nn_conv3x3_{kind}_weights"
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        u = torch.empty(getattr(L, name + "_bytes")(Cout, Cin) // 2, dtype=torch.bfloat16, device=weight.device)
+        with torch.cuda.device(weight.device):
+            ret = getattr(L, name)(torch.cuda.current_stream(weight.device).cuda_stream, weight.data_ptr(), u.data_ptr(),
+                                   Cout, Cin)
+        _check(ret, name, "gd_nn_conv_last_error")
+        setattr(weight, attr, u)
+        setattr(weight, attr + "_key", key)
+    return u
+
+
+# C entries of the tiled kernels: (plain, GroupNorm in the loader); both take the statistics buffer last
+_TILED_ENTRY = {"patch": ("gd_nn_conv3x3_forward_stats", "gd_nn_conv3x3_gn_forward_stats"),
+                "wino": ("gd_nn_conv3x3_wino_forward", "gd_nn_conv3x3_wino_gn_forward"),
+                "wide": ("gd_nn_conv3x3_wide_forward", "gd_nn_conv3x3_wide_gn_forward")}
+
+
+def _tiled_launch(kind, x, w_khwc, bias, residual, out_channels, stat_part=None, gn=None):
+    """3x3/s1/p1 convolution on one of the tiled kernels: kind "patch" (patch-staged, LDS-DMA patch), "wino" (Winograd
+    F(2,3) along x, csrc/nn_conv_wino.h) or "wide" (128 channels x 16x32 pixels, csrc/nn_conv_wide.h).  gn = (mean_rstd,
+    gamma, beta, groups, silu) applies GroupNorm(+SiLU) in the loader, ``mean_rstd`` from gd_nn_groupnorm_stats /
+    finish_partials; ``stat_part`` receives the epilogue's partial sums (gd_nn_conv3x3_stat_rows)."""
     N, Cin, H, W = x.shape
     L = lib()
     y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
     bias, stride = _bias_and_stride(bias)
+    wp = w_khwc if kind == "patch" else _packed(w_khwc, kind)
+    plain_name, gn_name = _TILED_ENTRY[kind]
+    if gn is not None:
+        mr, gw, gb, groups, silu = gn
+        name, head = gn_name, (mr.data_ptr(), gw.data_ptr(), gb.data_ptr(), groups, int(silu))
+    elif kind == "patch" and stat_part is None:
+        # the patch kernel's plain entry insists on statistics and on its own routing rule: without statistics, its
+        # GroupNorm entry with no GroupNorm (the same launch as gd_nn_conv3x3_gn_forward)
+        name, head = gn_name, (None, None, None, 0, 0)
+    else:
+        name, head = plain_name, ()
     with torch.cuda.device(x.device):
-        ret = L.gd_nn_conv3x3_gn_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), None, None, None,
-                                         0, 0, w_khwc.data_ptr(), None if bias is None else bias.data_ptr(), stride,
-                                         None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W, Cin,
-                                         out_channels)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_conv3x3_gn_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+        ret = getattr(L, name)(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), *head, wp.data_ptr(),
+                               None if bias is None else bias.data_ptr(), stride,
+                               None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W, Cin, out_channels,
+                               None if stat_part is None else stat_part.data_ptr())
+    _check(ret, name, "gd_nn_conv_last_error")
     return y
 
 
-def _wino(weight):
-    """Cached Winograd F(2,3) filter bank (the kernel's 32 KB step images, include/gd_nn.h) of a frozen conv weight
-    (channels_last, i.e. [Cout][3][3][Cin] in memory) -- also of a flipped dgrad weight tensor."""
-    u = getattr(weight, "_gd_wino", None)
-    key = (weight.data_ptr(), weight._version)
-    if u is None or u.device != weight.device or getattr(weight, "_gd_wino_key", None) != key:
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        u = torch.empty(lib().gd_nn_conv3x3_wino_weights_bytes(Cout, Cin) // 2, dtype=torch.bfloat16, device=weight.device)
-        with torch.cuda.device(weight.device):
-            ret = lib().gd_nn_conv3x3_wino_weights(torch.cuda.current_stream(weight.device).cuda_stream,
-                                                   weight.data_ptr(), u.data_ptr(), Cout, Cin)
-        _check(ret, "gd_nn_conv3x3_wino_weights", "gd_nn_conv_last_error")
-        weight._gd_wino, weight._gd_wino_key = u, key
-    return u
+def _patch_launch(x, w_khwc, bias, residual, out_channels):
+    return _tiled_launch("patch", x, w_khwc, bias, residual, out_channels)
 
 
 def _wino_launch(x, w_khwc, bias, residual, out_channels, stat_part=None):
-    """Plain 3x3/s1/p1 convolution on the Winograd F(2,3)-along-x kernel (csrc/nn_conv_wino.h)."""
-    N, Cin, H, W = x.shape
-    L = lib()
-    y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    bias, stride = _bias_and_stride(bias)
-    u = _wino(w_khwc)
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_conv3x3_wino_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), u.data_ptr(),
-                                           None if bias is None else bias.data_ptr(), stride,
-                                           None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W, Cin,
-                                           out_channels, None if stat_part is None else stat_part.data_ptr())
-    _check(ret, "gd_nn_conv3x3_wino_forward", "gd_nn_conv_last_error")
-    return y
-
-
-def _wide(weight):
-    """Cached re-packing of a frozen conv weight for the wide-tile kernel (24 KB step images, include/gd_nn.h)."""
-    u = getattr(weight, "_gd_wide", None)
-    key = (weight.data_ptr(), weight._version)
-    if u is None or u.device != weight.device or getattr(weight, "_gd_wide_key", None) != key:
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        u = torch.empty(lib().gd_nn_conv3x3_wide_weights_bytes(Cout, Cin) // 2, dtype=torch.bfloat16, device=weight.device)
-        with torch.cuda.device(weight.device):
-            ret = lib().gd_nn_conv3x3_wide_weights(torch.cuda.current_stream(weight.device).cuda_stream,
-                                                   weight.data_ptr(), u.data_ptr(), Cout, Cin)
-        _check(ret, "gd_nn_conv3x3_wide_weights", "gd_nn_conv_last_error")
-        weight._gd_wide, weight._gd_wide_key = u, key
-    return u
+    return _tiled_launch("wino", x, w_khwc, bias, residual, out_channels, stat_part)
 
 
 def _wide_launch(x, w_khwc, bias, residual, out_channels, stat_part=None, gn=None):
-    """3x3/s1/p1 convolution on the 128-channel x 16x32-pixel tile (csrc/nn_conv_wide.h); gn = (mean_rstd, gamma, beta,
-    groups, silu) applies GroupNorm(+SiLU) in the loader."""
-    N, Cin, H, W = x.shape
-    L = lib()
-    y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    bias, stride = _bias_and_stride(bias)
-    u = _wide(w_khwc)
-    with torch.cuda.device(x.device):
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        tail = (u.data_ptr(), None if bias is None else bias.data_ptr(), stride, None if residual is None else residual.data_ptr(),
-                y.data_ptr(), N, H, W, Cin, out_channels, None if stat_part is None else stat_part.data_ptr())
-        if gn is None:
-            ret = L.gd_nn_conv3x3_wide_forward(st, x.data_ptr(), *tail)
-        else:
-            mr, gw, gb, groups, silu = gn
-            ret = L.gd_nn_conv3x3_wide_gn_forward(st, x.data_ptr(), mr.data_ptr(), gw.data_ptr(), gb.data_ptr(), groups,
-                                                  int(silu), *tail)
-    _check(ret, "gd_nn_conv3x3_wide_forward", "gd_nn_conv_last_error")
-    return y
+    return _tiled_launch("wide", x, w_khwc, bias, residual, out_channels, stat_part, gn)
 
 
 def _wino_gn_launch(x, mean_rstd, gn_weight, gn_bias, groups, silu, w_khwc, bias, residual, out_channels, stat_part=None):
-    """conv3x3(act(GroupNorm(x))) on the Winograd kernel, GroupNorm(+SiLU) applied in its loader; ``mean_rstd`` from
-    gd_nn_groupnorm_stats / finish_partials."""
-    N, Cin, H, W = x.shape
-    L = lib()
-    y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    bias, stride = _bias_and_stride(bias)
-    u = _wino(w_khwc)
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_conv3x3_wino_gn_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-                                              mean_rstd.data_ptr(), gn_weight.data_ptr(), gn_bias.data_ptr(), groups,
-                                              int(silu), u.data_ptr(), None if bias is None else bias.data_ptr(), stride,
-                                              None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W, Cin,
-                                              out_channels, None if stat_part is None else stat_part.data_ptr())
-    _check(ret, "gd_nn_conv3x3_wino_gn_forward", "gd_nn_conv_last_error")
-    return y
+    return _tiled_launch("wino", x, w_khwc, bias, residual, out_channels, stat_part, (mean_rstd, gn_weight, gn_bias, groups, silu))
 
 
 def _flipped(weight):
@@ -1086,24 +1052,12 @@ def _gnconv_forward(x, gw, gb, groups, eps, w, bias, residual, mr=None, next_nor
     part = torch.empty(N * (Cout // 4) * rows * 2, dtype=torch.float32, device=x.device) if rows else None
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        y = torch.empty((N, Cout, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        bias_c, stride = _bias_and_stride(bias)
-        bias_p = None if bias_c is None else bias_c.data_ptr()
-        res_p = None if residual is None else residual.data_ptr()
         if fused:
             if not have_mr:
                 _check(L.gd_nn_groupnorm_stats(stream, x.data_ptr(), N, H * W, Cin, groups, float(eps), ws.data_ptr(),
                                                mr.data_ptr()), "gd_nn_groupnorm_stats")
-            if _conv_route(N, H, W, Cin, Cout, gn=True) == "wide":
-                ret = L.gd_nn_conv3x3_wide_gn_forward(stream, x.data_ptr(), mr.data_ptr(), gw.data_ptr(), gb.data_ptr(),
-                                                      groups, 1, _wide(w).data_ptr(), bias_p, stride, res_p, y.data_ptr(),
-                                                      N, H, W, Cin, Cout, None if part is None else part.data_ptr())
-            else:
-                ret = L.gd_nn_conv3x3_gn_forward_stats(stream, x.data_ptr(), mr.data_ptr(), gw.data_ptr(), gb.data_ptr(),
-                                                   groups, 1, w.data_ptr(), bias_p, stride, res_p, y.data_ptr(), N, H, W,
-                                                   Cin, Cout, None if part is None else part.data_ptr())
-            if ret < 0:
-                raise RuntimeError(f"gd_nn_conv3x3_gn_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+            kind = "wide" if _conv_route(N, H, W, Cin, Cout, gn=True) == "wide" else "patch"
+            y = _tiled_launch(kind, x, w, bias, residual, Cout, part, (mr, gw, gb, groups, True))
         else:
             act = torch.empty_like(x, memory_format=torch.channels_last)
             _check(L.gd_nn_groupnorm_silu_forward(stream, x.data_ptr(), act.data_ptr(), gw.data_ptr(), gb.data_ptr(), N,
@@ -1111,18 +1065,7 @@ def _gnconv_forward(x, gw, gb, groups, eps, w, bias, residual, mr=None, next_nor
                                                   mr.data_ptr()), "gd_nn_groupnorm_silu_forward")
             if part is None:
                 return _conv_launch(act, w, bias, residual, Cout), mr, None
-            route = _conv_route(N, H, W, Cin, Cout)
-            if route == "wino":
-                ret = L.gd_nn_conv3x3_wino_forward(stream, act.data_ptr(), _wino(w).data_ptr(), bias_p, stride, res_p,
-                                                   y.data_ptr(), N, H, W, Cin, Cout, part.data_ptr())
-            elif route == "wide":
-                ret = L.gd_nn_conv3x3_wide_forward(stream, act.data_ptr(), _wide(w).data_ptr(), bias_p, stride, res_p,
-                                                   y.data_ptr(), N, H, W, Cin, Cout, part.data_ptr())
-            else:
-                ret = L.gd_nn_conv3x3_forward_stats(stream, act.data_ptr(), w.data_ptr(), bias_p, stride, res_p, y.data_ptr(),
-                                                    N, H, W, Cin, Cout, part.data_ptr())
-            if ret < 0:
-                raise RuntimeError(f"gd_nn_conv3x3_forward_stats failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+            y = _tiled_launch(_conv_route(N, H, W, Cin, Cout) or "patch", act, w, bias, residual, Cout, part)
         mr_next = None
         if part is not None:
             g2, eps2 = next_norm

@@ -1712,6 +1712,65 @@ def test_conv_routing_picks_the_measured_kernel_and_all_routes_agree():
     assert torch.equal(ys[1], ys[3])         # 128 wide tiles are too few: the router sent this shape to the Winograd kernel
 
 
+def test_conv_profile_counts_one_record_with_the_algorithmic_flops_and_bytes_per_entry_call():
+    """The event profile behind bench.py's roofline line: every entry call of the convolution family is ONE record of
+    2 * M * Cout * taps * Cin flops and 2 * (input elements + taps * Cin * Cout + M * Cout [+ M * Cout with a residual]) bytes
+    -- a split-K launch with its reduce is one record, the four parity classes of the upsample-fused convolution are one
+    record whose input counts once.  Integers held in doubles: compared for equality.  Each case once without and once with
+    a residual, but the upsample-fused entry, which takes none."""
+    from garmentdreamer_amd import nn_ops
+    g = torch.Generator(DEV).manual_seed(11)
+    cl = torch.channels_last
+
+    def act(*shape):
+        return torch.randn(*shape, device=DEV, generator=g).to(torch.bfloat16).contiguous(memory_format=cl)
+
+    def filt(co, ci):
+        return (torch.randn(co, ci, 3, 3, device=DEV, generator=g) / 30).to(torch.bfloat16).contiguous(memory_format=cl)
+
+    def conv_case(call, N, Cin, Cout, H, W):      # nine taps, stride 1
+        x, w = act(N, Cin, H, W), filt(Cout, Cin)
+        M = N * H * W
+        return [(lambda r=r: call(x, w, None, r, Cout), 2 * M * Cout * 9 * Cin,
+                 2 * (M * Cin + 9 * Cin * Cout + M * Cout + (M * Cout if r is not None else 0)))
+                for r in (None, act(N, Cout, H, W))]
+
+    def forced_split(x, w, b, r, co):
+        nn_ops.lib().gd_nn_conv_force_split(2)
+        try:
+            return nn_ops._conv_launch(x, w, b, r, co)
+        finally:
+            nn_ops.lib().gd_nn_conv_force_split(-1)
+
+    cases = conv_case(nn_ops._conv_launch, 1, 64, 64, 8, 8)            # implicit GEMM, unsplit
+    cases += conv_case(forced_split, 1, 128, 64, 8, 8)                 # split-K + reduce
+    cases += conv_case(nn_ops._patch_launch, 1, 64, 64, 16, 16)
+    cases += conv_case(nn_ops._wino_launch, 1, 32, 64, 16, 32)
+    cases += conv_case(nn_ops._wide_launch, 1, 32, 64, 16, 32)
+    xu, wu = act(1, 64, 8, 8), filt(64, 64)                            # four classes of 64 pixels, four taps each
+    cases.append((lambda: nn_ops.upsample2x_conv3x3(xu, wu), 4 * 2 * 64 * 64 * 4 * 64,
+                  2 * (64 * 64 + 4 * (4 * 64 * 64 + 64 * 64))))
+    xl = torch.randn(128, 64, device=DEV, generator=g).to(torch.bfloat16)
+    wl = (torch.randn(64, 64, device=DEV, generator=g) / 8).to(torch.bfloat16)
+    for r in (None, torch.randn(128, 64, device=DEV, generator=g).to(torch.bfloat16)):     # one tap
+        cases.append((lambda r=r: nn_ops.linear(xl, wl, None, r), 2 * 128 * 64 * 64,
+                      2 * (128 * 64 + 64 * 64 + 128 * 64 + (128 * 64 if r is not None else 0))))
+    assert nn_ops.lib().gd_nn_conv3x3_ws_bytes(1, 8, 8, 64, 64) == 0          # the first case is indeed unsplit
+    nn_ops.conv_profile(enable=True, reset=True)
+    try:
+        with torch.no_grad():
+            for call, flops, nbytes in cases:
+                _, n0, f0 = nn_ops.conv_profile()
+                b0 = nn_ops.conv_profile_bytes()
+                call()
+                _, n1, f1 = nn_ops.conv_profile()
+                assert n1 - n0 == 1
+                assert f1 - f0 == flops
+                assert nn_ops.conv_profile_bytes() - b0 == nbytes
+    finally:
+        nn_ops.conv_profile(enable=False, reset=True)
+
+
 _STEP_CONV_SHAPES = [   # (N, Cin, Cout, H): every stride-1 3x3 shape of the 8-view step that leaves the direct kernels (profiles/r04_conv_shapes.txt)
     (8, 128, 128, 512), (8, 256, 128, 256), (8, 512, 256, 128), (8, 512, 512, 128), (8, 512, 512, 64),
     (16, 320, 320, 64), (16, 640, 320, 64), (16, 960, 320, 64), (16, 640, 640, 64), (16, 320, 640, 32), (16, 640, 640, 32),

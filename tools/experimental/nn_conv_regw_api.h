@@ -16,9 +16,7 @@ int gd_nn_conv3x3_regw_weights(void* stream, const void* weight, void* u)
     if (!weight || !u) return fail(GD_NN_ERR_INVALID_ARG, "regw_weights: null pointer");
     hipLaunchKernelGGL(conv3x3_regw_weights_kernel, dim3(72), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)weight,
                        (uint16_t*)u);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 int gd_nn_conv3x3_regw_supported(int N, int H, int W, int Cin, int Cout)
@@ -35,8 +33,8 @@ int gd_nn_conv3x3_regw_forward(void* stream, const void* x, const void* u, const
     if (residual) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_regw: no residual form");
     if (!gd_nn_conv3x3_regw_supported(N, H, W, Cin, Cout))
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_regw: need Cin = Cout = 128, H % 16 == 0, W % 32 == 0, tensors < 2 GiB");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
+    const int dev = current_device();
+    if (dev < 0) return dev;
     hipStream_t s = (hipStream_t)stream;
     // column strips of 32 pixels, cut into vertical segments (multiples of 16 rows) until the grid fills the chip twice
     const int strips = W / 32;
@@ -47,35 +45,17 @@ int gd_nn_conv3x3_regw_forward(void* stream, const void* x, const void* u, const
     segs = (H + seg_rows - 1) / seg_rows;
     const int nwg = N * strips * segs;
     const int64_t M = (int64_t)N * H * W;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
+    ProfScope prof(s);
 #define GD_LAUNCH_RW(STAT_)                                                                                        \
     do {                                                                                                           \
-        auto kern = conv3x3_regw_kernel<STAT_>;                                                                    \
-        static bool attr_set[16] = {false};                                                                        \
-        if (!attr_set[dev]) {                                                                                      \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kRegwLds);    \
-            attr_set[dev] = true;                                                                                  \
-        }                                                                                                          \
+        constexpr auto kern = conv3x3_regw_kernel<STAT_>;                                                          \
+        if (const int r = reserve_lds<kern>(dev, kRegwLds)) return r;                                              \
         hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), kRegwLds, s, (const uint16_t*)x, (const uint16_t*)u,        \
                            (const uint16_t*)bias, bias_img_stride, (uint16_t*)y, N, H, W, strips, segs, seg_rows,  \
                            nwg, stat_part);                                                                        \
     } while (0)
     if (stat_part) GD_LAUNCH_RW(true); else GD_LAUNCH_RW(false);
 #undef GD_LAUNCH_RW
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        g_cprof.total_flops += 2.0 * (double)M * Cout * 9.0 * Cin;
-        g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout +
-                                      (residual ? (double)M * Cout : 0.0));
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    prof.close_s1(M, Cin, Cout, residual != nullptr);
+    return launch_status();
 }

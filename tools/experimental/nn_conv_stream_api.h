@@ -51,9 +51,7 @@ int gd_nn_conv3x3_stream_weights(void* stream, const void* weight, void* wp, int
     const size_t total = (size_t)(Cout / 32) * 9 * (Cin / 16) * 64;
     hipLaunchKernelGGL(conv3x3_stream_weights_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256),
                        0, (hipStream_t)stream, (const uint16_t*)weight, (uint4*)wp, Cout, Cin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    return launch_status();
 }
 
 size_t gd_nn_conv3x3_stream_ws_bytes(int N, int H, int W, int Cin, int Cout)
@@ -71,25 +69,16 @@ int gd_nn_conv3x3_stream_forward(void* stream, const void* x, const void* wp, co
     if (!stream_plan(N, H, W, Cin, Cout, &p))
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_stream: need N*H*W <= 512, Cin >= 64 and % 16 == 0, Cout >= 64 and % 32 == 0");
     if (ws_bytes < gd_nn_conv3x3_stream_ws_bytes(N, H, W, Cin, Cout)) return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_stream: workspace too small");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return fail(GD_NN_ERR_HIP, "hipGetDevice failed");
+    const int dev = current_device();
+    if (dev < 0) return dev;
     hipStream_t s = (hipStream_t)stream;
     const int M = N * H * W;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (g_cprof.on) {
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        ea = g_cprof.get(); eb = g_cprof.get();
-        if (ea && eb) (void)hipEventRecord(ea, s);
-    }
+    ProfScope prof(s);
 #define GD_LAUNCH_ST(FA_, FB_)                                                                                        \
     do {                                                                                                              \
-        auto kern = conv3x3_stream_kernel<FA_, FB_>;                                                                  \
+        constexpr auto kern = conv3x3_stream_kernel<FA_, FB_>;                                                        \
         constexpr int lds = (kStreamWaves / 2) * FA_ * FB_ * 1024 * 4;                                                \
-        static bool attr_set[16] = {false};                                                                           \
-        if (!attr_set[dev]) {                                                                                         \
-            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);            \
-            attr_set[dev] = true;                                                                                     \
-        }                                                                                                             \
+        if (const int r = reserve_lds<kern>(dev, lds)) return r;                                                      \
         hipLaunchKernelGGL(kern, dim3(p.tiles_n, p.groups, p.tiles_m), dim3(64 * kStreamWaves), lds, s,               \
                            (const uint16_t*)x, (const uint4*)wp, (float*)ws, N, H, W, Cin, p.steps_total,             \
                            p.steps_per_wave);                                                                         \
@@ -102,15 +91,7 @@ int gd_nn_conv3x3_stream_forward(void* stream, const void* x, const void* wp, co
     else if (p.fa == 2 && p.fb == 4) GD_LAUNCH_ST(2, 4);
     else GD_LAUNCH_ST(1, 8);
 #undef GD_LAUNCH_ST
-    if (ea && eb) {
-        (void)hipEventRecord(eb, s);
-        std::lock_guard<std::mutex> lk(g_cprof.mu);
-        g_cprof.pending.push_back({ea, eb});
-        g_cprof.total_flops += 2.0 * (double)M * Cout * 9.0 * Cin;
-        g_cprof.total_bytes += 2.0 * ((double)M * Cin + 9.0 * Cin * Cout + (double)M * Cout + (residual ? (double)M * Cout : 0.0));
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GD_NN_ERR_HIP, hipGetErrorString(e));
-    return GD_NN_OK;
+    prof.close_s1(M, Cin, Cout, residual != nullptr);
+    return launch_status();
 }
 
