@@ -134,6 +134,27 @@ MESH_GEOMETRY_SIGNATURES = {
     "gd_mesh_normal_consistency_backward": (_i, [_vp] + [_i] * 2 + [_vp] * 4),     # stream, F P, fn face_nbr dloss dfn
 }
 
+# the NeTF stage's texture field: hash-grid encoding and the fused albedo MLP (include/gd_texture.h)
+TEXTURE_MAX_LEVELS = 16
+
+
+class TextureLayout(C.Structure):
+    """``gd_texture_layout``, passed by value"""
+    _fields_ = [("num_levels", C.c_int32), ("scale", C.c_float * TEXTURE_MAX_LEVELS),
+                ("res", C.c_int32 * TEXTURE_MAX_LEVELS), ("size", C.c_int32 * TEXTURE_MAX_LEVELS),
+                ("offset", C.c_int32 * (TEXTURE_MAX_LEVELS + 1))]
+
+
+TEXTURE_SIGNATURES = {
+    "gd_texture_encode_forward": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout, _vp]),       # stream, N, x mask grid, layout, enc
+    "gd_texture_encode_backward": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout, _vp]),      # stream, N, x mask denc, layout, dgrid
+    "gd_texture_field_forward": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout] + [_vp] * 5), # ..., w1 b1 w2 b2 color
+    "gd_texture_field_backward_scratch_bytes": (C.c_size_t, [_i]),
+    "gd_texture_field_backward": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout] + [_vp] * 12),  # ..., w1 b1 w2 b2 color dcolor
+                                                                                               # dgrid dw1 db1 dw2 db2 scratch
+    "gd_texture_last_error": (C.c_char_p, []),
+}
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -161,7 +182,8 @@ def lib():
         except OSError as e:  # e.g. libamdhip64 missing
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
-                + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()):
+                + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
+                + list(TEXTURE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,463 @@
+"""The NeTF stage's texture field: ``color = sigmoid(mlp(encoder(xyz)))`` of ``Renderer.render``
+(Garment_Deformer_NeTF/netf/render/mesh_renderer.py:368-375), with the multiresolution hash grid of
+netf/render/texture_encoder.py:8-37 (tiny-cuda-nn's "Grid"/"Hash", linear interpolation) on the HIP kernels of
+``csrc/raster_texture.hip`` (C-ABI and definitions: include/gd_texture.h) -- no CPU path.
+
+  * ``grid_layout(...)``      the level table (numpy, float64), handed to the kernels by value
+  * ``HashGridEncoder``       the reference's module: ``forward(x, bound=1)`` -> [N, 32]
+  * ``TextureField``          the fused field, ``forward(x, mask=None)`` -> [N, 3]; ``.encoder`` / ``.mlp`` are the unfused
+                              pair over the same parameters; ``optimizer()`` steps grid and MLP with one launch
+  * ``NeTFRenderer``          ``MeshRenderer`` that evaluates a field on every pixel with the coverage as ``mask``: no
+                              ``mask.any()``, no boolean indexing, nothing that waits for the GPU
+
+Gradients follow ``.grad`` semantics at the C level (every kernel ADDS into the buffer it is given).  A parameter that
+``TextureFieldOptimizer`` has re-seated carries ``_gd_grad_sink`` (a view of the optimizer's flat gradient buffer, as
+``flat_adam.FlatAdam`` gives the LoRA adapters): the backward adds straight into it and returns nothing to autograd.
+Without a sink the backward allocates a zeroed gradient and returns it.  There is no gradient to ``x``: the live
+configuration has ``fix_geo: true``; ``x.requires_grad`` raises.  The gradient to the grid is accumulated with float
+atomics (as tiny-cuda-nn does): its last bits differ between runs; the MLP gradients and every forward are reproducible.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _native
+from .mesh_render import MeshRenderer, antialias, antialias_weights, interpolate, rasterize, safe_normalize
+
+FEATURES = 2
+FIELD_WIDTH = 32
+_X_GRAD = ("gradients with respect to the sample positions are not implemented: detach x, or keep the geometry fixed "
+           "(fix_geo: true)")
+
+
+class GridLayout(NamedTuple):
+    num_levels: int
+    scale: np.ndarray      # float32 [L]: s_l
+    res: np.ndarray        # int64 [L]
+    size: np.ndarray       # int64 [L], entries
+    offset: np.ndarray     # int64 [L + 1], entries
+    dense: np.ndarray      # bool [L]
+
+    @property
+    def num_entries(self) -> int:
+        return int(self.offset[-1])
+
+    @property
+    def num_params(self) -> int:
+        return self.num_entries * FEATURES
+
+    @property
+    def output_dim(self) -> int:
+        return self.num_levels * FEATURES
+
+    def struct(self) -> "_native.TextureLayout":
+        s = _native.TextureLayout()
+        s.num_levels = self.num_levels
+        for l in range(self.num_levels):
+            s.scale[l], s.res[l], s.size[l], s.offset[l] = float(self.scale[l]), int(self.res[l]), int(self.size[l]), \
+                int(self.offset[l])
+        s.offset[self.num_levels] = int(self.offset[-1])
+        return s
+
+
+def grid_layout(num_levels: int = 16, base_resolution: int = 16, per_level_scale: Optional[float] = None,
+                log2_hashmap_size: int = 19, desired_resolution: int = 1024) -> GridLayout:
+    """The level table of include/gd_texture.h.  ``per_level_scale`` defaults to the reference's
+    ``exp2(log2(desired_resolution / num_levels) / (num_levels - 1))``."""
+    if not 1 <= num_levels <= _native.TEXTURE_MAX_LEVELS:
+        raise ValueError(f"grid_layout: num_levels must be in 1..{_native.TEXTURE_MAX_LEVELS}")
+    if not 1 <= log2_hashmap_size <= 24:
+        raise ValueError("grid_layout: log2_hashmap_size must be in 1..24")
+    if base_resolution < 1:
+        raise ValueError("grid_layout: base_resolution must be >= 1")
+    if per_level_scale is None:
+        per_level_scale = np.exp2(np.log2(desired_resolution / num_levels) / max(num_levels - 1, 1))
+    if not per_level_scale >= 1.0:
+        raise ValueError("grid_layout: per_level_scale must be >= 1")
+    levels = np.arange(num_levels, dtype=np.float64)
+    scale = (np.power(2.0, levels * np.log2(np.float64(per_level_scale))) * base_resolution - 1.0).astype(np.float32)
+    res = np.ceil(scale.astype(np.float64)).astype(np.int64) + 1
+    if res.max() > 1 << 21:
+        raise ValueError("grid_layout: a level's resolution exceeds 2^21")
+    size = np.minimum((res ** 3 + 7) // 8 * 8, 1 << log2_hashmap_size)
+    offset = np.concatenate(([0], np.cumsum(size))).astype(np.int64)
+    return GridLayout(num_levels, scale, res, size, offset, res ** 3 <= size)
+
+
+def _check(ret: int, what: str) -> None:
+    if ret < 0:
+        raise RuntimeError(f"{what} failed ({ret}): {_native.lib().gd_texture_last_error().decode('utf-8', 'replace')}")
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _gpu(name: str, what: str, t, dtype) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: the HIP kernels have no CPU path ({what} must be on the GPU)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: {what} must be {dtype}")
+    return t
+
+
+def _points(name: str, x, mask):
+    """(x [N,3] contiguous and detached, mask uint8 [N] or None)"""
+    _gpu(name, "x", x, torch.float32)
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name}: x must be [N,3]")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name}: " + _X_GRAD)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+            raise RuntimeError(f"{name}: the HIP kernels have no CPU path (mask must be on the GPU)")
+        if mask.numel() != x.shape[0]:
+            raise ValueError(f"{name}: mask must have one element per point")
+        mask = mask.reshape(-1)
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)          # same bytes: True is 1
+        elif mask.dtype != torch.uint8:
+            raise TypeError(f"{name}: mask must be bool or uint8")
+        mask = mask.contiguous()
+    return x.detach().contiguous(), mask
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _sinks(params):
+    """``Parameter._gd_grad_sink`` of each (read in the forward: autograd hands the backward other tensor objects)"""
+    return [getattr(p, "_gd_grad_sink", None) for p in params]
+
+
+def _grad_targets(params, sinks):
+    """per parameter: (buffer the kernel adds into, what autograd gets back)"""
+    out = []
+    for p, sink in zip(params, sinks):
+        if sink is not None and sink.shape == p.shape and sink.is_contiguous():
+            out.append((sink, None))
+        else:
+            g = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            out.append((g, g))
+    return out
+
+
+class _Encode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, grid, layout, struct):
+        dev = x.device
+        enc = torch.empty((x.shape[0], layout.output_dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check(_native.lib().gd_texture_encode_forward(_stream(dev), x.shape[0], x.data_ptr(), _ptr(mask),
+                                                           grid.data_ptr(), struct, enc.data_ptr()),
+                   "gd_texture_encode_forward")
+        ctx.save_for_backward(x, mask if mask is not None else x.new_empty(0), grid)
+        ctx.has_mask, ctx.struct, ctx.sinks = mask is not None, struct, _sinks([grid])
+        return enc
+
+    @staticmethod
+    def backward(ctx, denc):
+        x, mask, grid = ctx.saved_tensors
+        dev = x.device
+        denc = denc.contiguous()
+        (buf, ret), = _grad_targets([grid], ctx.sinks)
+        with torch.cuda.device(dev):
+            _check(_native.lib().gd_texture_encode_backward(_stream(dev), x.shape[0], x.data_ptr(),
+                                                            mask.data_ptr() if ctx.has_mask else None, denc.data_ptr(),
+                                                            ctx.struct, buf.data_ptr()), "gd_texture_encode_backward")
+        return None, None, ret, None, None
+
+
+class _Field(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, mask, grid, w1, b1, w2, b2, struct):
+        dev = x.device
+        color = torch.empty((x.shape[0], 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _check(_native.lib().gd_texture_field_forward(_stream(dev), x.shape[0], x.data_ptr(), _ptr(mask),
+                                                          grid.data_ptr(), struct, w1.data_ptr(), b1.data_ptr(),
+                                                          w2.data_ptr(), b2.data_ptr(), color.data_ptr()),
+                   "gd_texture_field_forward")
+        ctx.save_for_backward(x, mask if mask is not None else x.new_empty(0), grid, w1, b1, w2, b2, color)
+        ctx.has_mask, ctx.struct, ctx.sinks = mask is not None, struct, _sinks([grid, w1, b1, w2, b2])
+        return color
+
+    @staticmethod
+    def backward(ctx, dcolor):
+        x, mask, grid, w1, b1, w2, b2, color = ctx.saved_tensors
+        dev = x.device
+        n = x.shape[0]
+        L = _native.lib()
+        dcolor = dcolor.contiguous()
+        targets = _grad_targets([grid, w1, b1, w2, b2], ctx.sinks)
+        scratch = torch.empty(max(L.gd_texture_field_backward_scratch_bytes(n), 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _check(L.gd_texture_field_backward(_stream(dev), n, x.data_ptr(), mask.data_ptr() if ctx.has_mask else None,
+                                               grid.data_ptr(), ctx.struct, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                                               b2.data_ptr(), color.data_ptr(), dcolor.data_ptr(),
+                                               *[t[0].data_ptr() for t in targets], scratch.data_ptr()),
+                   "gd_texture_field_backward")
+        return (None, None) + tuple(t[1] for t in targets) + (None,)
+
+
+def _param(name: str, what: str, p: torch.Tensor, shape) -> torch.Tensor:
+    _gpu(name, what, p, torch.float32)
+    if tuple(p.shape) != tuple(shape) or not p.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous {tuple(shape)} tensor")
+    return p
+
+
+def encode(x: torch.Tensor, grid: torch.Tensor, layout: GridLayout, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``enc`` float32 [N, L F] of the points ``x`` [N,3] (in [-1, 1]^3; anything finite is defined) in the flat table
+    ``grid``; rows with ``mask == 0`` or a non-finite coordinate are 0 and pass no gradient."""
+    _param("encode", "grid", grid, (layout.num_params,))
+    x, mask = _points("encode", x, mask)
+    return _Encode.apply(x, mask, grid, layout, layout.struct())
+
+
+def field(x: torch.Tensor, grid: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+          layout: GridLayout, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``color`` float32 [N,3] = sigmoid(W2 relu(W1 enc + b1) + b2), one launch; needs ``L F = 32``."""
+    if layout.output_dim != FIELD_WIDTH:
+        raise ValueError(f"field: the fused path needs num_levels * level_dim = {FIELD_WIDTH}")
+    _param("field", "grid", grid, (layout.num_params,))
+    _param("field", "w1", w1, (FIELD_WIDTH, FIELD_WIDTH))
+    _param("field", "b1", b1, (FIELD_WIDTH,))
+    _param("field", "w2", w2, (3, FIELD_WIDTH))
+    _param("field", "b2", b2, (3,))
+    x, mask = _points("field", x, mask)
+    return _Field.apply(x, mask, grid, w1, b1, w2, b2, layout.struct())
+
+
+class HashGridEncoder(nn.Module):
+    """The reference's ``HashGridEncoder`` (texture_encoder.py:8-37): same signature, same ``per_level_scale``; ``params`` is
+    the flat table in tiny-cuda-nn's order (level, entry, feature), uniform in [-1e-4, 1e-4]."""
+
+    def __init__(self, input_dim=3, num_levels=16, level_dim=2, log2_hashmap_size=19, base_resolution=16,
+                 desired_resolution=1024, interpolation="linear", generator: Optional[torch.Generator] = None):
+        super().__init__()
+        if input_dim != 3 or level_dim != FEATURES:
+            raise NotImplementedError("HashGridEncoder: only input_dim=3 and level_dim=2 are built")
+        if interpolation != "linear":
+            raise NotImplementedError("HashGridEncoder: only linear interpolation is built (the reference never asks "
+                                      "for smoothstep)")
+        self._set_layout(grid_layout(num_levels, base_resolution, None, log2_hashmap_size, desired_resolution), generator)
+
+    def _set_layout(self, layout: GridLayout, generator):
+        self.layout = layout
+        self.input_dim = 3
+        self.output_dim = layout.output_dim
+        self.params = nn.Parameter((torch.rand(layout.num_params, generator=generator) * 2 - 1) * 1e-4)
+
+    @classmethod
+    def from_layout(cls, layout: GridLayout, generator: Optional[torch.Generator] = None) -> "HashGridEncoder":
+        """An encoder over any ``grid_layout(...)`` (the constructor's arguments cannot state ``per_level_scale``)."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self._set_layout(layout, generator)
+        return self
+
+    def forward(self, x, bound=1, mask=None):
+        if bound != 1:
+            raise ValueError("HashGridEncoder: only bound=1 is built")
+        return encode(x, self.params, self.layout, mask)
+
+
+WEIGHT_GRAD_BLOCK = 128
+
+
+def _blocked_outer(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """``dy^T x`` [out,in] over the rows of ``dy`` [n,out] and ``x`` [n,in]: one small product per block of 128 rows, then
+    the sum of the blocks.  ``nn.Linear``'s backward issues one GEMM ``dy.t().mm(x)``, a single running fp32 sum per entry
+    over all n rows; the stage sums over ~10^5 pixels, where that sum is 4.0e-6 of the largest entry from float64 on
+    MI355X and the blocked one 1.6e-7."""
+    n = x.shape[0]
+    if n == 0:
+        return x.new_zeros(dy.shape[1], x.shape[1])
+    blocks = (n + WEIGHT_GRAD_BLOCK - 1) // WEIGHT_GRAD_BLOCK
+    pad = blocks * WEIGHT_GRAD_BLOCK - n
+    if pad:
+        dy, x = F.pad(dy, (0, 0, 0, pad)), F.pad(x, (0, 0, 0, pad))
+    part = torch.bmm(dy.reshape(blocks, WEIGHT_GRAD_BLOCK, -1).transpose(1, 2), x.reshape(blocks, WEIGHT_GRAD_BLOCK, -1))
+    return part.sum(dim=0)
+
+
+class _BlockedLinear(torch.autograd.Function):
+    """``F.linear`` on [..., in] whose weight gradient is ``_blocked_outer`` over all leading dimensions"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        return F.linear(x, weight, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dx = dy @ weight if ctx.needs_input_grad[0] else None
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        return dx, _blocked_outer(dy2, x.reshape(-1, x.shape[-1])), dy2.sum(dim=0)
+
+
+class AlbedoMLP(nn.Module):
+    """The reference's ``MLP(32, 3, 32, 2)`` (texture_encoder.py:93-112): two ``nn.Linear`` with a ReLU between; same
+    parameters, same forward, the weight gradients summed in blocks (``_blocked_outer``).  Input [..., 32].  The gradients
+    reach ``.grad`` through autograd; where ``TextureFieldOptimizer`` has made ``.grad`` a view of its flat buffer, autograd
+    accumulates into that view in place (what ``FlatAdam`` relies on for its non-LoRA producers)."""
+
+    def __init__(self, dim_in=FIELD_WIDTH, dim_out=3, dim_hidden=FIELD_WIDTH):
+        super().__init__()
+        self.net = nn.ModuleList([nn.Linear(dim_in, dim_hidden), nn.Linear(dim_hidden, dim_out)])
+
+    def forward(self, x):
+        l1, l2 = self.net
+        return _BlockedLinear.apply(F.relu(_BlockedLinear.apply(x, l1.weight, l1.bias)), l2.weight, l2.bias)
+
+
+class TextureField(nn.Module):
+    """``sigmoid(mlp(encoder(x)))`` in one launch forward, and one launch plus the fixed-order sum backward.
+    ``encoder``: a ``HashGridEncoder`` with ``output_dim == 32`` (default: the reference's).  ``generator`` seeds the grid;
+    the MLP is ``nn.Linear``-initialised from torch's global generator."""
+
+    def __init__(self, encoder: Optional[HashGridEncoder] = None, generator: Optional[torch.Generator] = None):
+        super().__init__()
+        self.encoder = encoder if encoder is not None else HashGridEncoder(generator=generator)
+        if self.encoder.output_dim != FIELD_WIDTH:
+            raise ValueError(f"TextureField: the fused path needs an encoder with output_dim = {FIELD_WIDTH}")
+        self.mlp = AlbedoMLP()
+
+    def forward(self, x, mask=None):
+        l1, l2 = self.mlp.net
+        return field(x, self.encoder.params, l1.weight, l1.bias, l2.weight, l2.bias, self.encoder.layout, mask)
+
+    def unfused(self, x, mask=None):
+        """The same function through ``.encoder`` and ``.mlp`` (the [N,32] encoding goes through memory)."""
+        color = torch.sigmoid(self.mlp(self.encoder(x, mask=mask)))
+        if mask is None:
+            return color * torch.isfinite(x).all(dim=1, keepdim=True)
+        return color * (torch.isfinite(x).all(dim=1) & (mask.reshape(-1) != 0))[:, None]
+
+    def get_params(self, hashgrid_lr=0.01, mlp_lr=0.001):
+        """The reference's two groups (mesh_renderer.py:248-253)."""
+        return [{"params": list(self.encoder.parameters()), "lr": hashgrid_lr},
+                {"params": list(self.mlp.parameters()), "lr": mlp_lr}]
+
+    def optimizer(self, hashgrid_lr=0.01, mlp_lr=0.001, betas=(0.9, 0.999), eps=1e-8) -> "TextureFieldOptimizer":
+        return TextureFieldOptimizer(self, hashgrid_lr, mlp_lr, betas, eps)
+
+
+class TextureFieldOptimizer:
+    """``torch.optim.Adam(field.get_params(...))`` as ONE ``gd_scene_adam_step`` launch over one flat buffer holding the
+    grid and then the MLP, the two ranges with their own learning rate; ``zero_grad`` is ONE memset.  The parameters are
+    re-seated as views of the flat buffer NOW and their ``.grad`` are, for good, views of the flat gradient buffer, into
+    which the field's backward adds directly.  As with ``FlatAdam``: a parameter always has a gradient here (zeros if
+    nothing wrote one), so its moments decay on every step."""
+
+    def __init__(self, field_module: TextureField, hashgrid_lr=0.01, mlp_lr=0.001, betas=(0.9, 0.999), eps=1e-8):
+        grid = [field_module.encoder.params]
+        mlp = list(field_module.mlp.parameters())
+        for p in grid + mlp:
+            _gpu("TextureFieldOptimizer", "every parameter", p, torch.float32)
+        dev = grid[0].device
+        pad = lambda k: (k + 63) // 64 * 64          # every view starts 256-byte aligned
+        n_grid = pad(grid[0].numel())
+        n = n_grid + sum(pad(p.numel()) for p in mlp)
+        self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._grad = torch.zeros(n, dtype=torch.float32, device=dev)          # padding stays 0: its update is 0 / (0 + eps)
+        self._exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
+        off = 0
+        with torch.no_grad():
+            for p in grid + mlp:
+                k = p.numel()
+                view = self._flat[off:off + k].view(p.shape)
+                view.copy_(p.data)
+                p.data = view
+                gview = self._grad[off:off + k].view(p.shape)
+                p.grad = gview
+                p._gd_grad_sink = gview
+                off += pad(k)
+        self._ends = (C.c_int64 * 2)(n_grid, n)
+        self.param_groups = [{"params": grid, "lr": float(hashgrid_lr)}, {"params": mlp, "lr": float(mlp_lr)}]
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.step_count = 0
+
+    def zero_grad(self, set_to_none: bool = False):
+        self._grad.zero_()
+
+    @torch.no_grad()
+    def step(self):
+        self.step_count += 1
+        lrs = (C.c_double * 2)(float(self.param_groups[0]["lr"]), float(self.param_groups[1]["lr"]))
+        dev = self._flat.device
+        with torch.cuda.device(dev):
+            _native.check_scene(_native.lib().gd_scene_adam_step(
+                _stream(dev), self._flat.data_ptr(), self._grad.data_ptr(), self._exp_avg.data_ptr(),
+                self._exp_avg_sq.data_ptr(), self._flat.numel(), 2, self._ends, lrs, self.betas[0], self.betas[1],
+                self.eps, self.step_count), "gd_scene_adam_step")
+
+
+class NeTFRenderer(MeshRenderer):
+    """``MeshRenderer`` for a field that takes the coverage as an argument: ``texture_fn(xyzs [H W,3], mask uint8 [H W])``
+    -> [H W,3] with zeros where ``mask == 0`` (a ``TextureField``).  Same outputs as ``MeshRenderer.render``, bit for bit:
+    the pose is inverted by the same device routine as ``torch.inverse`` but through ``torch.linalg.inv_ex``, which leaves
+    the status on the device where ``torch.inverse`` reads it back (a host inverse differs from the device's in the last
+    bit, and with it every barycentric), and the matrices go up in one asynchronous copy from pinned memory.  torch issues
+    no synchronisation in a render, its backward and an optimizer step (``torch.cuda.set_sync_debug_mode("error")``); that
+    mode sees torch's own synchronisation points, not a wait inside the solver library behind ``inv_ex``, which is not
+    excluded by it.  A singular or non-finite pose raises, as in ``MeshRenderer``; it is detected on the host."""
+
+    def _upload(self, pose, proj):
+        """device float32 [3,4,4]: inverse pose, projection, pose"""
+        pose = np.asarray(pose).astype(np.float32)
+        try:
+            ok = bool(np.isfinite(np.linalg.inv(pose)).all())
+        except np.linalg.LinAlgError:
+            ok = False
+        if not ok:
+            raise torch.linalg.LinAlgError("NeTFRenderer: the pose is singular or not finite")
+        mats = np.stack([pose, np.asarray(proj)]).astype(np.float32)
+        mats = torch.from_numpy(mats).pin_memory().to(self.v.device, non_blocking=True)
+        return torch.stack([torch.linalg.inv_ex(mats[0]).inverse, mats[1], mats[0]])
+
+    def _clip(self, mats):
+        v_cam = torch.matmul(F.pad(self.v, pad=(0, 1), mode="constant", value=1.0), mats[0].T).float()
+        return v_cam, (v_cam @ mats[1].T).contiguous()
+
+    def clip_positions(self, pose, proj):
+        return self._clip(self._upload(pose, proj))
+
+    def render(self, pose, proj, h0, w0, ssaa=1, bg_color=1):
+        if ssaa != 1:
+            raise ValueError("NeTFRenderer.render: ssaa != 1 is not implemented (the reference's trainer passes 1)")
+        h, w = int(h0), int(w0)
+        v, f, topo = self.v, self.f, self.topology
+        mats = self._upload(pose, proj)
+        v_cam, v_clip = self._clip(mats)
+
+        rast = rasterize(v_clip, f, (h, w))
+        wts = antialias_weights(rast, v_clip, f, topo)
+
+        alpha = torch.clamp(rast[..., -1:], 0, 1).contiguous()
+        alpha = antialias(alpha, rast, v_clip, f, weights=wts).clamp(0, 1)
+        depth = interpolate(-v_cam[..., 2:3].contiguous(), rast, f)     # a slice: a list index would upload its indices
+        xyzs_ = interpolate(v, rast, f)
+        mask = (alpha > 0).view(-1)
+        color = self.texture_fn(xyzs_.view(-1, 3), mask).float().view(h, w, 3)
+        color = antialias(color, rast, v_clip, f, weights=wts).clamp(0, 1)
+        color = alpha * color + (1 - alpha) * bg_color
+
+        normal_ = interpolate(self.vn, rast, f)
+        normal = safe_normalize(normal_)
+        with torch.no_grad():
+            position = antialias(xyzs_, rast, v_clip, f, weights=wts)
+            normal_aa = antialias(normal_, rast, v_clip, f, weights=wts)
+            view_direction = F.normalize(position - mats[2][:3, 3], dim=-1)
+            cosines_view = F.cosine_similarity(view_direction, normal_aa, dim=-1, eps=1e-6)
+        return {"image": color, "alpha": alpha, "depth": depth, "normal": (normal + 1) / 2, "cosinesview": cosines_view}
