@@ -155,6 +155,15 @@ TEXTURE_SIGNATURES = {
     "gd_texture_last_error": (C.c_char_p, []),
 }
 
+# the texture bake's padding: nearest covered texel and the 8-bit gather (include/gd_bake.h)
+BAKE_MAX_PADDING = 64
+BAKE_MAX_CHANNELS = 4
+BAKE_SIGNATURES = {
+    "gd_bake_pad_index": (_i, [_vp] + [_i] * 3 + [_vp] * 2),                       # stream, H W padding, mask src
+    "gd_bake_resolve_u8": (_i, [_vp] + [_i] * 3 + [_vp] * 3),                      # stream, H W C, image src out
+    "gd_bake_last_error": (C.c_char_p, []),
+}
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -183,7 +192,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
-                + list(TEXTURE_SIGNATURES.items()):
+                + list(TEXTURE_SIGNATURES.items()) + list(BAKE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

@@ -72,6 +72,23 @@ def save_image_rgba(path: str, rgb, mask) -> str:
     return path
 
 
+def save_image_rgb(path: str, rgb8) -> str:
+    """uint8 [H,W,3] (numpy or torch) -> 8-bit RGB PNG, bytes as given, row 0 first (the baked albedo of
+    ``texture_bake.write_textured_obj``)."""
+    img8 = rgb8.detach().cpu().numpy() if hasattr(rgb8, "detach") else np.asarray(rgb8)
+    if img8.dtype != np.uint8 or img8.ndim != 3 or img8.shape[2] != 3:
+        raise ValueError("save_image_rgb: the image must be uint8 [H,W,3]")
+    H, W = img8.shape[:2]
+    raw = np.concatenate((np.zeros((H, 1), np.uint8), img8.reshape(H, W * 3)), axis=1).tobytes()   # filter 0 per row
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(_png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)))   # 8-bit, colour type 2 = RGB
+        f.write(_png_chunk(b"IDAT", zlib.compress(raw, 6)))
+        f.write(_png_chunk(b"IEND", b""))
+    return path
+
+
 def dump_test_view(save_dir: str, out: Dict, batch: Dict, camera_info_list: List[Dict], alpha_threshold: float = 0.5,
                    view: int = 0):
     """``test_step`` (GaussianDreamer.py:334-410) for one rendered view: thresholded alpha as the mask, RGBA PNG

@@ -3,6 +3,7 @@
 (Garment_3DGS/threestudio/systems/GaussianDreamer.py:115-177), without ``open3d``:
 
   * ``load_obj``            ``v`` / ``f`` lines of a Wavefront OBJ (numpy);
+  * ``load_obj_uv``         the same with the ``vt`` lines and ``a/b`` corners (what ``texture_bake`` writes);
   * ``sample_surface``      area-uniform surface samples, seeded, float64 (numpy; init-time work, not a hot path);
   * ``shell_search``        nearest sample of every query within a fixed radius: the HIP kernels of
                             ``csrc/raster_template.hip`` (``gd_scene_shell_search``, include/gd_scene.h) -- no CPU path.
@@ -67,6 +68,67 @@ def load_obj(path: str) -> Tuple[np.ndarray, np.ndarray]:
     if fa.max() >= v.shape[0]:
         raise ValueError(f"{path}: vertex index {int(fa.max()) + 1} out of range ({v.shape[0]} vertices)")
     return v, fa
+
+
+def load_obj_uv(path: str):
+    """``load_obj`` plus the texture coordinates: (v float64 [V,3], f int64 [F,3], vt float64 [T,2], ft int64 [F,3]) from
+    the ``v``, ``vt`` and ``f`` lines; a corner is ``a/b`` or ``a/b/c``.  ``vt`` and ``ft`` are ``None`` when any corner of
+    any face has no texture index (``a`` or ``a//c``).  Polygons, negative indices (relative to the ``v`` / ``vt`` read so
+    far) and the errors follow ``load_obj``; ``vt`` is returned as written (``write_textured_obj`` writes ``1 - v``)."""
+    verts, coords, faces, tfaces = [], [], [], []
+    textured = True
+
+    def index(tok, t, count, lineno, what):
+        i = int(t)
+        if i < 0:
+            i += count
+            if i < 0:
+                raise ValueError(f"{path}:{lineno}: relative {what} index {tok} out of range")
+            return i
+        if i == 0:
+            raise ValueError(f"{path}:{lineno}: {what} index 0 (OBJ indices start at 1)")
+        return i - 1
+
+    with open(path, "r") as f:
+        for lineno, line in enumerate(f, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{lineno}: a vertex needs three coordinates")
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+            elif tok[0] == "vt":
+                if len(tok) < 3:
+                    raise ValueError(f"{path}:{lineno}: a texture coordinate needs two components")
+                coords.append((float(tok[1]), float(tok[2])))
+            elif tok[0] == "f":
+                corners, tcorners = [], []
+                for t in tok[1:]:
+                    parts = t.split("/")
+                    corners.append(index(t, parts[0], len(verts), lineno, "vertex"))
+                    if len(parts) > 1 and parts[1]:
+                        tcorners.append(index(t, parts[1], len(coords), lineno, "texture"))
+                    else:
+                        textured = False
+                if len(corners) < 3:
+                    raise ValueError(f"{path}:{lineno}: a face needs at least three corners")
+                faces += [(corners[0], corners[k], corners[k + 1]) for k in range(1, len(corners) - 1)]
+                if textured:
+                    tfaces += [(tcorners[0], tcorners[k], tcorners[k + 1]) for k in range(1, len(tcorners) - 1)]
+    if not faces:
+        raise ValueError(f"{path}: no faces")
+    v = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    fa = np.asarray(faces, dtype=np.int64)
+    if fa.max() >= v.shape[0]:
+        raise ValueError(f"{path}: vertex index {int(fa.max()) + 1} out of range ({v.shape[0]} vertices)")
+    if not textured:
+        return v, fa, None, None
+    vt = np.asarray(coords, dtype=np.float64).reshape(-1, 2)
+    ft = np.asarray(tfaces, dtype=np.int64)
+    if ft.max() >= vt.shape[0]:
+        raise ValueError(f"{path}: texture index {int(ft.max()) + 1} out of range ({vt.shape[0]} texture coordinates)")
+    return v, fa, vt, ft
 
 
 def sample_surface(vertices, faces, n: int, seed: int) -> np.ndarray:

@@ -9,6 +9,8 @@ netf/render/texture_encoder.py:8-37 (tiny-cuda-nn's "Grid"/"Hash", linear interp
                               pair over the same parameters; ``optimizer()`` steps grid and MLP with one launch
   * ``NeTFRenderer``          ``MeshRenderer`` that evaluates a field on every pixel with the coverage as ``mask``: no
                               ``mask.any()``, no boolean indexing, nothing that waits for the GPU
+                              ``export_mesh`` bakes the field into a UV atlas and writes the textured OBJ
+                              (``texture_bake.py``)
 
 Gradients follow ``.grad`` semantics at the C level (every kernel ADDS into the buffer it is given).  A parameter that
 ``TextureFieldOptimizer`` has re-seated carries ``_gd_grad_sink`` (a view of the optimizer's flat gradient buffer, as
@@ -432,6 +434,14 @@ class NeTFRenderer(MeshRenderer):
 
     def clip_positions(self, pose, proj):
         return self._clip(self._upload(pose, proj))
+
+    def export_mesh(self, save_path, texture_resolution=2048, padding=16, reverse=False, vt=None, ft=None):
+        """``Renderer.export_mesh`` (mesh_renderer.py:260-313) plus optional UVs: bakes ``texture_fn`` into the atlas ``vt`` /
+        ``ft`` (``texture_bake.grid_atlas`` of the mesh if not given: one chart per triangle, seam-heavy) and writes
+        ``save_path`` with its ``.mtl`` and ``_albedo.png``; returns the three paths.  Waits for the GPU (once per run)."""
+        from . import texture_bake
+        return texture_bake.export_textured_mesh(save_path, self.texture_fn, self.v, self.f, texture_resolution, padding,
+                                                 reverse, vt, ft)
 
     def render(self, pose, proj, h0, w0, ssaa=1, bg_color=1):
         if ssaa != 1:
