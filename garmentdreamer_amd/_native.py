@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libgd_raster.so")
@@ -200,17 +201,36 @@ def lib():
     return _lib
 
 
-def check(ret: int, what: str) -> int:
+# prefix of an entry's name -> the symbol that holds its message, longest prefix first (gd_scene_densify_stats lives in
+# raster_scene.hip with the scene entries; plan and apply in raster_densify.hip have a channel of their own)
+_ERROR_CHANNELS = (("gd_scene_densify_stats", "gd_scene_last_error"), ("gd_scene_densify_", "gd_scene_densify_last_error"),
+                   ("gd_scene_", "gd_scene_last_error"), ("gd_mesh_", "gd_mesh_last_error"),
+                   ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
+                   ("gd_raster_", "gd_raster_last_error"))
+
+
+def error_channel(name: str) -> str:
+    """The ``gd_*_last_error`` symbol that holds the message of a failed ``name``: the one of its longest prefix."""
+    for prefix, channel in _ERROR_CHANNELS:
+        if name.startswith(prefix):
+            return channel
+    raise KeyError(f"{name} belongs to no error channel of libgd_raster.so")
+
+
+def checked(name: str, ret: int, channel: Optional[str] = None) -> int:
+    """``ret`` of the entry ``name`` if it is not negative; else ``RuntimeError`` with the text of its error channel."""
     if ret < 0:
-        msg = lib().gd_raster_last_error().decode("utf-8", "replace")
-        raise RuntimeError(f"{what} failed ({ret}): {msg}")
+        text = getattr(lib(), channel or error_channel(name))().decode("utf-8", "replace")
+        raise RuntimeError(f"{name} failed ({ret}): {text}")
     return ret
+
+
+def check(ret: int, what: str) -> int:
+    return ret if ret >= 0 else checked(what, ret, "gd_raster_last_error")
 
 
 def check_scene(ret: int, what: str, err: str = "gd_scene_last_error") -> int:
-    if ret < 0:
-        raise RuntimeError(f"{what} failed ({ret}): {getattr(lib(), err)().decode('utf-8', 'replace')}")
-    return ret
+    return ret if ret >= 0 else checked(what, ret, err)
 
 
 KERNEL_IDS = {"preprocess": 0, "scan": 1, "duplicate": 2, "sort": 3, "ranges": 4, "render_fwd": 5, "render_bwd": 6,

@@ -14,9 +14,9 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import mesh_geometry as mg
+from ._launch import require_gpu
 from .flat_adam import FlatAdam
 from .mesh_deform import GBufferRenderer
-from .mesh_render import _gpu
 
 FIRST_STAGE_WEIGHTS = {"mask": 2, "normal_consistency": 0.1, "laplacian": 800}   # deformation.py, loss_weights_first
 CHANNELS = ["mask", "position", "normal"]
@@ -30,16 +30,15 @@ class Deformer:
 
     def __init__(self, vertices: torch.Tensor, indices: torch.Tensor, mvps, target_masks: Sequence[torch.Tensor],
                  resolutions, lr: float = 1e-3, weights: Optional[Dict[str, float]] = None):
-        _gpu("Deformer", "vertices", vertices, torch.float32, 3)
-        if not isinstance(indices, torch.Tensor) or not indices.is_cuda:
-            raise RuntimeError("Deformer: the HIP kernels have no CPU path (indices must be on the GPU)")
+        require_gpu("Deformer", "vertices", vertices, torch.float32, 3)
+        require_gpu("Deformer", "indices", indices)
         dev = vertices.device
         self.initial = vertices.detach().clone().contiguous()
         self.geometry = mg.build_geometry(indices, num_vertices=vertices.shape[0], device=dev)
         self.renderer = GBufferRenderer()
         mvps, self.resolutions = GBufferRenderer._views(mvps, resolutions)
         self.mvps = [torch.as_tensor(m, dtype=torch.float32).to(dev) for m in mvps]
-        self.target_masks = [_gpu("Deformer", "target mask", m, torch.float32, 1) for m in target_masks]
+        self.target_masks = [require_gpu("Deformer", "target mask", m, torch.float32, 1) for m in target_masks]
         if len(self.target_masks) != len(self.mvps):
             raise ValueError("Deformer: one target mask per view")
         self.weights = dict(FIRST_STAGE_WEIGHTS if weights is None else weights)

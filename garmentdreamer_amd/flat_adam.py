@@ -36,6 +36,34 @@ import torch
 from . import _native
 
 
+def padded(k: int) -> int:
+    """``k`` floats rounded up to 64: every view starts 256-byte aligned (the LoRA kernels read 16-byte vectors)"""
+    return (k + 63) // 64 * 64
+
+
+def reseat(params):
+    """Re-seat the fp32 GPU parameters ``params`` NOW as views of one flat buffer, each at a ``padded`` offset, and make
+    their ``.grad`` and ``_gd_grad_sink``, for good, views of one flat gradient buffer.  Returns (flat, grad, exp_avg,
+    exp_avg_sq, the gradient views in the order of ``params``); the buffers live on the first parameter's device."""
+    dev = params[0].device
+    n = sum(padded(p.numel()) for p in params)
+    flat, grad, exp_avg, exp_avg_sq = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(4))
+    grad_views = []                           # grad's padding stays 0: its update is 0 / (0 + eps)
+    off = 0
+    with torch.no_grad():
+        for p in params:
+            k = p.numel()
+            view = flat[off:off + k].view(p.shape)
+            view.copy_(p.data)
+            p.data = view                     # the module keeps its Parameter objects; their storage is the flat buffer
+            gview = grad[off:off + k].view(p.shape)
+            p.grad = gview                    # for good: zero_grad() clears the buffer, it does not drop the views
+            p._gd_grad_sink = gview           # the backward kernels add into it (nn_ops._grad_sinks, texture_field._sinks)
+            grad_views.append(gview)
+            off += padded(k)
+    return flat, grad, exp_avg, exp_avg_sq, grad_views
+
+
 class FlatAdam:
     def __init__(self, params: Iterable[torch.Tensor], lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  flat: Optional[Iterable[torch.Tensor]] = None, exclude: Iterable[torch.Tensor] = (),
@@ -75,26 +103,8 @@ class FlatAdam:
         dev = flat[0].device
         if any(p.device != dev for p in flat):
             raise ValueError("FlatAdam: the fp32 parameters must live on one device")
-        pad = lambda k: (k + 63) // 64 * 64      # every view starts 256-byte aligned (the LoRA kernels read 16-byte vectors)
-        n = sum(pad(p.numel()) for p in flat)
-        self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._grad = torch.zeros(n, dtype=torch.float32, device=dev)       # padding stays 0: its update is 0 / (0 + eps)
-        self._exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._grad_views = []
-        off = 0
-        with torch.no_grad():
-            for p in flat:
-                k = p.numel()
-                view = self._flat[off:off + k].view(p.shape)
-                view.copy_(p.data)
-                p.data = view                     # the module keeps its Parameter objects; their storage is the flat buffer
-                gview = self._grad[off:off + k].view(p.shape)
-                p.grad = gview                    # for good: zero_grad() clears the buffer, it does not drop the views
-                p._gd_grad_sink = gview           # the LoRA backward kernels add into it (nn_ops._grad_sinks)
-                self._grad_views.append(gview)
-                off += pad(k)
-        self._ends = (C.c_int64 * 1)(n)
+        self._flat, self._grad, self._exp_avg, self._exp_avg_sq, self._grad_views = reseat(flat)
+        self._ends = (C.c_int64 * 1)(self._flat.numel())
 
     # ---- torch.optim.Optimizer surface the training loops use ---------------------------------------------------
     def zero_grad(self, set_to_none: bool = True):

@@ -2,7 +2,8 @@
 (Garment_Deformer_NeTF/deformer/core/renderer.py:104-164; ``deformation.py`` runs Adam on vertex offsets through it), on
 the HIP kernels of ``csrc/raster_mesh.hip`` (C-ABI: include/gd_mesh_deform.h; definitions: include/gd_mesh.h) -- no CPU
 path.  ``mesh_render`` keeps the fixed-geometry ops, which refuse positions that require a gradient; the ops here have the
-same forward, bit for bit, and add the gradients to vertex positions:
+same forward, bit for bit (both modules call the autograd functions of ``_mesh_ops``), and add the gradients to vertex
+positions:
 
   * ``rasterize(pos, tri, resolution, topology)``          ``rast`` with an autograd edge to ``pos`` (nvdiffrast's rast_db
                                                             path: the derivative of the barycentrics (u, v))
@@ -22,9 +23,10 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _native
-from . import mesh_render as _mr
-from .mesh_render import MAX_CHANNELS, MeshTopology, _check, _gpu, _stream, _unbatch, build_topology  # noqa: F401
+from . import _mesh_ops as ops
+from ._launch import launch, require_gpu
+from ._mesh_ops import MeshTopology, build_topology
+from .mesh_render import MAX_CHANNELS, antialias_weights  # noqa: F401  (MAX_CHANNELS: a public name of this module too)
 
 
 def _topology(name: str, topology: Optional[MeshTopology], tri: torch.Tensor, V: int) -> MeshTopology:
@@ -36,95 +38,23 @@ def _topology(name: str, topology: Optional[MeshTopology], tri: torch.Tensor, V:
     return topology
 
 
-def _scratch(nbytes: int, dev) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-
-
-class _Rasterize(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pos, tri, H, W, topology):
-        rast = _mr.rasterize(pos.detach(), tri, (H, W))
-        ctx.save_for_backward(pos, tri, rast)
-        ctx.topology = topology
-        return rast
-
-    @staticmethod
-    def backward(ctx, drast):
-        pos, tri, rast = ctx.saved_tensors
-        dev = pos.device
-        H, W = rast.shape[:2]
-        V, nf = pos.shape[0], tri.shape[0]
-        L = _native.lib()
-        drast = drast.contiguous()
-        dpos = torch.empty((V, 4), dtype=torch.float32, device=dev)
-        scratch = _scratch(L.gd_mesh_rasterize_backward_scratch_bytes(nf), dev)
-        with torch.cuda.device(dev):
-            _check(L.gd_mesh_rasterize_backward(_stream(dev), V, nf, H, W, pos.data_ptr(), tri.data_ptr(),
-                                                rast.data_ptr(), drast.data_ptr(), ctx.topology.corner_ptr.data_ptr(),
-                                                ctx.topology.corner_idx.data_ptr(), dpos.data_ptr(), scratch.data_ptr()),
-                   "gd_mesh_rasterize_backward")
-        return dpos, None, None, None, None
-
-
 def rasterize(pos: torch.Tensor, tri: torch.Tensor, resolution, topology: Optional[MeshTopology] = None) -> torch.Tensor:
     """``rast`` float32 [H,W,4] = (u, v, z/w, triangle id + 1) exactly as ``mesh_render.rasterize`` returns it, with an
     autograd edge to ``pos`` (float32 clip-space [V,4] or [1,V,4]): the gradient of ``rast[..., 0:2]`` reaches x, y and w
     of the covering triangle's corners; channels 2 and 3 pass none on.  ``topology``: ``build_topology(tri)``, built here
     if missing (a host pass over the mesh)."""
-    _gpu("rasterize", "pos", pos, torch.float32, 4)
-    _gpu("rasterize", "tri", tri, torch.int32, 3)
-    p, batched = _unbatch("rasterize", "pos", pos, 2)
+    require_gpu("rasterize", "pos", pos, torch.float32, 4)
+    require_gpu("rasterize", "tri", tri, torch.int32, 3)
+    p, batched = ops._unbatch("rasterize", "pos", pos, 2)
     if tri.dim() != 2:
         raise ValueError("rasterize: tri must be [F,3]")
     H, W = int(resolution[0]), int(resolution[1])
     t = tri.contiguous()
     if p.requires_grad and torch.is_grad_enabled():
-        rast = _Rasterize.apply(p.contiguous(), t, H, W, _topology("rasterize", topology, t, p.shape[0]))
+        rast = ops._Rasterize.apply(p.contiguous(), t, H, W, _topology("rasterize", topology, t, p.shape[0]))
     else:
-        rast = _mr.rasterize(p.detach(), t, (H, W))
+        rast = ops.rasterize_forward(p.detach().contiguous(), t, H, W)
     return rast[None] if batched else rast
-
-
-class _Interpolate(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, attr, rast, tri, pos, topology):
-        dev = attr.device
-        H, W = rast.shape[:2]
-        V, C = attr.shape
-        out = torch.empty((H, W, C), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_mesh_interpolate_forward(_stream(dev), V, tri.shape[0], C, H, W, attr.data_ptr(),
-                                                             rast.data_ptr(), tri.data_ptr(), out.data_ptr()),
-                   "gd_mesh_interpolate_forward")
-        ctx.save_for_backward(attr, rast, tri, pos)
-        ctx.topology = topology
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        attr, rast, tri, pos = ctx.saved_tensors
-        dev = rast.device
-        H, W = rast.shape[:2]
-        V, C = attr.shape
-        nf = tri.shape[0]
-        L = _native.lib()
-        dout = dout.contiguous()
-        dattr = drast = None
-        with torch.cuda.device(dev):
-            if ctx.needs_input_grad[0]:
-                dattr = torch.empty((V, C), dtype=torch.float32, device=dev)
-                scratch = _scratch(L.gd_mesh_interpolate_backward_scratch_bytes(nf, C), dev)
-                _check(L.gd_mesh_interpolate_backward(_stream(dev), V, nf, C, H, W, pos.data_ptr(), tri.data_ptr(),
-                                                      rast.data_ptr(), dout.data_ptr(),
-                                                      ctx.topology.corner_ptr.data_ptr(),
-                                                      ctx.topology.corner_idx.data_ptr(), dattr.data_ptr(),
-                                                      scratch.data_ptr()), "gd_mesh_interpolate_backward")
-            if ctx.needs_input_grad[1]:
-                drast = torch.empty((H, W, 4), dtype=torch.float32, device=dev)
-                _check(L.gd_mesh_interpolate_backward_rast(_stream(dev), V, nf, C, H, W, attr.data_ptr(), rast.data_ptr(),
-                                                           tri.data_ptr(), dout.data_ptr(), drast.data_ptr()),
-                       "gd_mesh_interpolate_backward_rast")
-        return dattr, drast, None, None, None
 
 
 def interpolate(attr: torch.Tensor, rast: torch.Tensor, tri: torch.Tensor, pos: torch.Tensor,
@@ -133,13 +63,13 @@ def interpolate(attr: torch.Tensor, rast: torch.Tensor, tri: torch.Tensor, pos: 
     (float32 [V,C], C <= 8) and in ``rast`` (which ``rasterize`` above carries on to the positions).  ``pos``: the
     positions ``rast`` was made from (the gradient to ``attr`` walks each triangle's pixel box again); it receives no
     gradient from this op itself."""
-    _gpu("interpolate", "attr", attr, torch.float32, None)
-    _gpu("interpolate", "rast", rast, torch.float32, 4)
-    _gpu("interpolate", "tri", tri, torch.int32, 3)
-    _gpu("interpolate", "pos", pos, torch.float32, 4)
-    a, b1 = _unbatch("interpolate", "attr", attr, 2)
-    r, b2 = _unbatch("interpolate", "rast", rast, 3)
-    p = _unbatch("interpolate", "pos", pos.detach(), 2)[0].contiguous()
+    require_gpu("interpolate", "attr", attr, torch.float32)
+    require_gpu("interpolate", "rast", rast, torch.float32, 4)
+    require_gpu("interpolate", "tri", tri, torch.int32, 3)
+    require_gpu("interpolate", "pos", pos, torch.float32, 4)
+    a, b1 = ops._unbatch("interpolate", "attr", attr, 2)
+    r, b2 = ops._unbatch("interpolate", "rast", rast, 3)
+    p = ops._unbatch("interpolate", "pos", pos.detach(), 2)[0].contiguous()
     if not 1 <= a.shape[1] <= MAX_CHANNELS:
         raise ValueError(f"interpolate: attr must have 1..{MAX_CHANNELS} channels")
     if p.shape[0] != a.shape[0]:
@@ -147,38 +77,8 @@ def interpolate(attr: torch.Tensor, rast: torch.Tensor, tri: torch.Tensor, pos: 
     t = tri.contiguous()
     if topology is not None or (a.requires_grad and torch.is_grad_enabled()):
         topology = _topology("interpolate", topology, t, a.shape[0])
-    out = _Interpolate.apply(a.contiguous(), r.contiguous(), t, p, topology)
+    out = ops._Interpolate.apply(a.contiguous(), r.contiguous(), t, p, topology)
     return out[None] if (b1 or b2) else out
-
-
-class _Antialias(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, color, pos, rast, tri, topology, wts):
-        ctx.save_for_backward(color, pos, rast, tri, wts)
-        ctx.topology = topology
-        return _mr._aa_apply(color, wts, False)
-
-    @staticmethod
-    def backward(ctx, dout):
-        color, pos, rast, tri, wts = ctx.saved_tensors
-        dout = dout.contiguous()
-        dcolor = _mr._aa_apply(dout, wts, True) if ctx.needs_input_grad[0] else None
-        dpos = None
-        if ctx.needs_input_grad[1]:
-            dev = pos.device
-            H, W, C = color.shape
-            V, nf = pos.shape[0], tri.shape[0]
-            topo = ctx.topology
-            L = _native.lib()
-            dpos = torch.empty((V, 4), dtype=torch.float32, device=dev)
-            scratch = _scratch(L.gd_mesh_antialias_backward_pos_scratch_bytes(nf), dev)
-            with torch.cuda.device(dev):
-                _check(L.gd_mesh_antialias_backward_pos(_stream(dev), V, nf, C, H, W, rast.data_ptr(), pos.data_ptr(),
-                                                        tri.data_ptr(), topo.opp.data_ptr(), color.data_ptr(),
-                                                        dout.data_ptr(), topo.corner_ptr.data_ptr(),
-                                                        topo.corner_idx.data_ptr(), dpos.data_ptr(), scratch.data_ptr()),
-                       "gd_mesh_antialias_backward_pos")
-        return dcolor, dpos, None, None, None, None
 
 
 def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: torch.Tensor,
@@ -188,23 +88,23 @@ def antialias(color: torch.Tensor, rast: torch.Tensor, pos: torch.Tensor, tri: t
     reaches the vertices.  ``weights=mesh_render.antialias_weights(rast, pos.detach(), tri, topology)`` shares the
     analysis between images of one (rast, pos); each image still gets its own gradient to ``pos``, because that gradient
     is computed from the image and its upstream gradient, not from the shared weights."""
-    _gpu("antialias", "color", color, torch.float32, None)
-    _gpu("antialias", "rast", rast, torch.float32, 4)
-    _gpu("antialias", "pos", pos, torch.float32, 4)
-    _gpu("antialias", "tri", tri, torch.int32, 3)
-    c, batched = _unbatch("antialias", "color", color, 3)
-    r = _unbatch("antialias", "rast", rast.detach(), 3)[0].contiguous()
-    p = _unbatch("antialias", "pos", pos, 2)[0].contiguous()
+    require_gpu("antialias", "color", color, torch.float32)
+    require_gpu("antialias", "rast", rast, torch.float32, 4)
+    require_gpu("antialias", "pos", pos, torch.float32, 4)
+    require_gpu("antialias", "tri", tri, torch.int32, 3)
+    c, batched = ops._unbatch("antialias", "color", color, 3)
+    r = ops._unbatch("antialias", "rast", rast.detach(), 3)[0].contiguous()
+    p = ops._unbatch("antialias", "pos", pos, 2)[0].contiguous()
     t = tri.contiguous()
     topology = _topology("antialias", topology, t, p.shape[0])
     topology = MeshTopology(topology.opp.contiguous(), topology.corner_ptr.contiguous(), topology.corner_idx.contiguous())
     if weights is None:
-        weights = _mr.antialias_weights(r, p.detach(), t, topology)
+        weights = antialias_weights(r, p.detach(), t, topology)
     else:
-        _gpu("antialias", "weights", weights, torch.float32, 4)
+        require_gpu("antialias", "weights", weights, torch.float32, 4)
     if tuple(r.shape[:2]) != tuple(c.shape[:2]) or tuple(weights.shape) != (c.shape[0], c.shape[1], 4):
         raise ValueError("antialias: rast and weights must be [H,W,4] of the colour's resolution")
-    out = _Antialias.apply(c.contiguous(), p, r, t, topology, weights.detach().contiguous())
+    out = ops._Antialias.apply(c.contiguous(), weights.detach().contiguous(), p, r, t, topology)
     return out[None] if batched else out
 
 
@@ -214,20 +114,16 @@ def visible_vertices(rasts, tri: torch.Tensor, num_vertices: int) -> torch.Tenso
     (renderer.py:104-126) as one launch per image that stores ones."""
     if isinstance(rasts, torch.Tensor):
         rasts = [rasts]
-    _gpu("visible_vertices", "tri", tri, torch.int32, 3)
+    require_gpu("visible_vertices", "tri", tri, torch.int32, 3)
     if tri.dim() != 2:
         raise ValueError("visible_vertices: tri must be [F,3]")
     t = tri.contiguous()
-    dev = t.device
     V = int(num_vertices)
-    vis = torch.zeros(max(V, 1), dtype=torch.uint8, device=dev)
-    L = _native.lib()
+    vis = torch.zeros(max(V, 1), dtype=torch.uint8, device=t.device)
     for rast in rasts:
-        _gpu("visible_vertices", "rast", rast, torch.float32, 4)
-        r = _unbatch("visible_vertices", "rast", rast.detach(), 3)[0].contiguous()
-        with torch.cuda.device(dev):
-            _check(L.gd_mesh_visible_vertices(_stream(dev), V, t.shape[0], r.shape[0] * r.shape[1], r.data_ptr(),
-                                              t.data_ptr(), vis.data_ptr()), "gd_mesh_visible_vertices")
+        require_gpu("visible_vertices", "rast", rast, torch.float32, 4)
+        r = ops._unbatch("visible_vertices", "rast", rast.detach(), 3)[0].contiguous()
+        launch("gd_mesh_visible_vertices", t.device, V, t.shape[0], r.shape[0] * r.shape[1], r, t, vis)
     return vis[:V].bool()
 
 
@@ -282,9 +178,8 @@ class GBufferRenderer:
 
     @staticmethod
     def _mesh(vertices, indices):
-        _gpu("GBufferRenderer", "vertices", vertices, torch.float32, 3)
-        if not isinstance(indices, torch.Tensor) or not indices.is_cuda:
-            raise RuntimeError("GBufferRenderer: the HIP kernels have no CPU path (indices must be on the GPU)")
+        require_gpu("GBufferRenderer", "vertices", vertices, torch.float32, 3)
+        require_gpu("GBufferRenderer", "indices", indices)
         if vertices.dim() != 2:
             raise ValueError("GBufferRenderer: vertices must be [V,3]")
         return indices.detach().int().contiguous()
@@ -297,7 +192,7 @@ class GBufferRenderer:
         or one for all.  Each view is rasterized once and analysed once for all its channels."""
         idx = self._mesh(vertices, indices)
         if "normal" in channels:
-            _gpu("GBufferRenderer", "vertex_normals", vertex_normals, torch.float32, 3)
+            require_gpu("GBufferRenderer", "vertex_normals", vertex_normals, torch.float32, 3)
         mvps, resolutions = self._views(mvps, resolutions)
         topo = _topology("GBufferRenderer", topology, idx, vertices.shape[0])
         gbuffers = []
@@ -305,7 +200,7 @@ class GBufferRenderer:
             gbuffer = {}
             pos = self.transform_pos(mvp, vertices)
             rast = rasterize(pos, idx, res, topo)
-            wts = _mr.antialias_weights(rast.detach(), pos.detach(), idx, topo) if with_antialiasing else None
+            wts = antialias_weights(rast.detach(), pos.detach(), idx, topo) if with_antialiasing else None
 
             def aa(x):
                 return antialias(x, rast, pos, idx, topo, weights=wts) if with_antialiasing else x

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _native
-from .mesh_render import MeshTopology, _check, _gpu, _stream, build_topology
+from ._launch import launch, require_gpu, scratch
+from ._mesh_ops import MeshTopology, build_topology, edge_groups, host_triangles
 
 
 class MeshGeometry(NamedTuple):
@@ -44,23 +45,10 @@ def build_geometry(tri, num_vertices: Optional[int] = None, device=None) -> Mesh
     by more than two triangles (the reference asserts the same).  Two faces that share three edges (duplicates) form three
     pairs, as in the reference.  A face that lists a vertex twice is outside the definitions: it forms no pair with itself
     and its edge (v, v), though listed in ``edges``, makes no vertex its own neighbour."""
-    if isinstance(tri, torch.Tensor):
-        device = tri.device if device is None else device
-        t = tri.detach().cpu().numpy()
-    else:
-        t = np.asarray(tri)
-    t = np.ascontiguousarray(t, dtype=np.int64).reshape(-1, 3)
+    t, nv, device = host_triangles(tri, num_vertices, device)
     nf = t.shape[0]
-    nv = int(num_vertices) if num_vertices is not None else (int(t.max()) + 1 if nf else 0)
     topology = build_topology(t, num_vertices=nv, device=device)       # checks the index range
-    # edge i of face f runs between corners i+1 and i+2; k = 3 f + i
-    lo = np.minimum(t[:, [1, 2, 0]], t[:, [2, 0, 1]]).ravel()
-    hi = np.maximum(t[:, [1, 2, 0]], t[:, [2, 0, 1]]).ravel()
-    key = lo * max(nv, 1) + hi
-    order = np.argsort(key, kind="stable")
-    sk = key[order]
-    start = np.flatnonzero(np.r_[True, sk[1:] != sk[:-1]]) if nf else np.zeros(0, np.int64)
-    count = np.diff(np.r_[start, sk.shape[0]])
+    lo, hi, order, start, count = edge_groups(t, nv)
     if nf and count.max() > 2:
         raise ValueError("build_geometry: an edge is shared by more than two triangles (non-manifold mesh)")
     edges = np.stack((lo[order[start]], hi[order[start]]), axis=1).reshape(-1, 2)
@@ -95,14 +83,6 @@ def _geometry(name: str, geo: MeshGeometry, V: Optional[int], F: Optional[int]) 
     return geo
 
 
-def _scratch(nbytes: int, dev) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
 class _Normals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, geo):
@@ -111,12 +91,8 @@ class _Normals(torch.autograd.Function):
         fn = torch.empty((nf, 3), dtype=torch.float32, device=dev)
         vn = torch.empty((V, 3), dtype=torch.float32, device=dev)
         length = torch.empty(V, dtype=torch.float32, device=dev)
-        topo = geo.topology
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_mesh_normals_forward(_stream(dev), V, nf, vertices.data_ptr(), geo.tri.data_ptr(),
-                                                         topo.corner_ptr.data_ptr(), topo.corner_idx.data_ptr(),
-                                                         fn.data_ptr(), vn.data_ptr(), length.data_ptr()),
-                   "gd_mesh_normals_forward")
+        launch("gd_mesh_normals_forward", dev, V, nf, vertices, geo.tri, geo.topology.corner_ptr,
+               geo.topology.corner_idx, fn, vn, length)
         ctx.save_for_backward(vertices, vn, length)
         ctx.geo = geo
         ctx.set_materialize_grads(False)
@@ -132,14 +108,9 @@ class _Normals(torch.autograd.Function):
             return None, None
         dfn = None if dfn is None else dfn.contiguous()
         dvn = None if dvn is None else dvn.contiguous()
-        L = _native.lib()
         dverts = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        scratch = _scratch(L.gd_mesh_normals_backward_scratch_bytes(nf), dev)
-        with torch.cuda.device(dev):
-            _check(L.gd_mesh_normals_backward(_stream(dev), V, nf, vertices.data_ptr(), geo.tri.data_ptr(),
-                                              topo.corner_ptr.data_ptr(), topo.corner_idx.data_ptr(), vn.data_ptr(),
-                                              length.data_ptr(), _ptr(dvn), _ptr(dfn), dverts.data_ptr(),
-                                              scratch.data_ptr()), "gd_mesh_normals_backward")
+        launch("gd_mesh_normals_backward", dev, V, nf, vertices, geo.tri, topo.corner_ptr, topo.corner_idx, vn, length,
+               dvn, dfn, dverts, scratch(_native.lib().gd_mesh_normals_backward_scratch_bytes(nf), dev))
         return dverts, None
 
 
@@ -147,7 +118,7 @@ def normals(vertices: torch.Tensor, geo: MeshGeometry):
     """``(face_normals [F,3], vertex_normals [V,3])`` of ``vertices`` (float32 [V,3]) as ``Mesh.compute_normals`` defines
     them: the normalised cross product per face, the normalised sum of the faces around a vertex (0 for a vertex no face
     uses), both with ``torch.nn.functional.normalize``'s 1e-12.  Differentiable in ``vertices`` through either output."""
-    _gpu("normals", "vertices", vertices, torch.float32, 3)
+    require_gpu("normals", "vertices", vertices, torch.float32, 3)
     if vertices.dim() != 2:
         raise ValueError("normals: vertices must be [V,3]")
     geo = _geometry("normals", geo, vertices.shape[0], None)
@@ -159,14 +130,10 @@ class _Laplacian(torch.autograd.Function):
     def forward(ctx, vertices, geo):
         dev = vertices.device
         V = vertices.shape[0]
-        L = _native.lib()
         delta = torch.empty((V, 3), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        scratch = _scratch(L.gd_mesh_loss_scratch_bytes(V), dev)
-        with torch.cuda.device(dev):
-            _check(L.gd_mesh_laplacian_forward(_stream(dev), V, geo.nbr_idx.shape[0], vertices.data_ptr(),
-                                               geo.nbr_ptr.data_ptr(), geo.nbr_idx.data_ptr(), delta.data_ptr(),
-                                               loss.data_ptr(), scratch.data_ptr()), "gd_mesh_laplacian_forward")
+        launch("gd_mesh_laplacian_forward", dev, V, geo.nbr_idx.shape[0], vertices, geo.nbr_ptr, geo.nbr_idx, delta, loss,
+               scratch(_native.lib().gd_mesh_loss_scratch_bytes(V), dev))
         ctx.save_for_backward(delta)
         ctx.geo = geo
         return loss
@@ -175,14 +142,10 @@ class _Laplacian(torch.autograd.Function):
     def backward(ctx, dloss):
         (delta,) = ctx.saved_tensors
         geo = ctx.geo
-        dev = delta.device
         V = delta.shape[0]
-        dloss = dloss.contiguous()
-        dverts = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_mesh_laplacian_backward(_stream(dev), V, geo.nbr_idx.shape[0], geo.nbr_ptr.data_ptr(),
-                                                            geo.nbr_idx.data_ptr(), delta.data_ptr(), dloss.data_ptr(),
-                                                            dverts.data_ptr()), "gd_mesh_laplacian_backward")
+        dverts = torch.empty((V, 3), dtype=torch.float32, device=delta.device)
+        launch("gd_mesh_laplacian_backward", delta.device, V, geo.nbr_idx.shape[0], geo.nbr_ptr, geo.nbr_idx, delta,
+               dloss.contiguous(), dverts)
         return dverts, None
 
 
@@ -191,13 +154,9 @@ class _NormalConsistency(torch.autograd.Function):
     def forward(ctx, fn, geo):
         dev = fn.device
         nf = fn.shape[0]
-        L = _native.lib()
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        scratch = _scratch(L.gd_mesh_loss_scratch_bytes(nf), dev)
-        with torch.cuda.device(dev):
-            _check(L.gd_mesh_normal_consistency_forward(_stream(dev), nf, geo.num_pairs, fn.data_ptr(),
-                                                        geo.face_nbr.data_ptr(), loss.data_ptr(), scratch.data_ptr()),
-                   "gd_mesh_normal_consistency_forward")
+        launch("gd_mesh_normal_consistency_forward", dev, nf, geo.num_pairs, fn, geo.face_nbr, loss,
+               scratch(_native.lib().gd_mesh_loss_scratch_bytes(nf), dev))
         ctx.save_for_backward(fn)
         ctx.geo = geo
         return loss
@@ -208,14 +167,9 @@ class _NormalConsistency(torch.autograd.Function):
         geo = ctx.geo
         dev = fn.device
         nf = fn.shape[0]
-        dloss = dloss.contiguous()
         dfn = torch.zeros((nf, 3), dtype=torch.float32, device=dev) if nf == 0 else \
             torch.empty((nf, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_mesh_normal_consistency_backward(_stream(dev), nf, geo.num_pairs, fn.data_ptr(),
-                                                                     geo.face_nbr.data_ptr(), dloss.data_ptr(),
-                                                                     dfn.data_ptr()),
-                   "gd_mesh_normal_consistency_backward")
+        launch("gd_mesh_normal_consistency_backward", dev, nf, geo.num_pairs, fn, geo.face_nbr, dloss.contiguous(), dfn)
         return dfn, None
 
 
@@ -226,9 +180,8 @@ class DeformMesh:
     over the mesh), which ``with_vertices`` shares."""
 
     def __init__(self, vertices: torch.Tensor, indices: torch.Tensor, geometry: Optional[MeshGeometry] = None):
-        _gpu("DeformMesh", "vertices", vertices, torch.float32, 3)
-        if not isinstance(indices, torch.Tensor) or not indices.is_cuda:
-            raise RuntimeError("DeformMesh: the HIP kernels have no CPU path (indices must be on the GPU)")
+        require_gpu("DeformMesh", "vertices", vertices, torch.float32, 3)
+        require_gpu("DeformMesh", "indices", indices)
         self.device = vertices.device
         self.vertices = vertices
         self.indices = indices.to(torch.int64)
@@ -265,7 +218,7 @@ def laplacian_loss(vertices: Union[torch.Tensor, DeformMesh], geo: Optional[Mesh
     ``geo``, or a ``DeformMesh``.  A 0-dim tensor on the device."""
     if isinstance(vertices, DeformMesh):
         vertices, geo = vertices.vertices, vertices.geometry
-    _gpu("laplacian_loss", "vertices", vertices, torch.float32, 3)
+    require_gpu("laplacian_loss", "vertices", vertices, torch.float32, 3)
     if vertices.dim() != 2:
         raise ValueError("laplacian_loss: vertices must be [V,3]")
     return _Laplacian.apply(vertices.contiguous(), _geometry("laplacian_loss", geo, vertices.shape[0], None))
@@ -277,7 +230,7 @@ def normal_consistency_loss(face_normals: Union[torch.Tensor, DeformMesh],
     float32 [F,3] with ``geo``, or a ``DeformMesh``.  A mesh without a pair gives 0 (the reference: NaN)."""
     if isinstance(face_normals, DeformMesh):
         face_normals, geo = face_normals.face_normals, face_normals.geometry
-    _gpu("normal_consistency_loss", "face_normals", face_normals, torch.float32, 3)
+    require_gpu("normal_consistency_loss", "face_normals", face_normals, torch.float32, 3)
     if face_normals.dim() != 2:
         raise ValueError("normal_consistency_loss: face_normals must be [F,3]")
     geo = _geometry("normal_consistency_loss", geo, None, face_normals.shape[0])

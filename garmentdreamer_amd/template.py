@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _native
+from ._launch import launch, scratch
 from .scene import SH_C0
 
 
@@ -169,14 +170,11 @@ def shell_search(samples: torch.Tensor, queries: torch.Tensor, radius: float) ->
     lo, hi = (C.c_float * 3)(*box[0].tolist()), (C.c_float * 3)(*box[1].tolist())
     L = _native.lib()
     edge, dims = C.c_float(0), (C.c_int * 3)()
-    _native.check_scene(L.gd_scene_shell_grid(lo, hi, float(radius), C.byref(edge), dims), "gd_scene_shell_grid")
+    _native.checked("gd_scene_shell_grid", L.gd_scene_shell_grid(lo, hi, float(radius), C.byref(edge), dims))
     nearest = torch.empty(Q, dtype=torch.int32, device=dev)
     dist2 = torch.empty(Q, dtype=torch.float32, device=dev)
-    scratch = torch.empty(L.gd_scene_shell_scratch_bytes(S, dims[0] * dims[1] * dims[2]), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _native.check_scene(L.gd_scene_shell_search(
-            torch.cuda.current_stream(dev).cuda_stream, S, smp.data_ptr(), Q, qry.data_ptr(), lo, hi, float(radius),
-            nearest.data_ptr(), dist2.data_ptr(), scratch.data_ptr()), "gd_scene_shell_search")
+    launch("gd_scene_shell_search", dev, S, smp, Q, qry, lo, hi, float(radius), nearest, dist2,
+           scratch(L.gd_scene_shell_scratch_bytes(S, dims[0] * dims[1] * dims[2]), dev))
     return nearest, dist2
 
 

@@ -24,7 +24,7 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
-from . import _native
+from ._launch import launch, require_gpu
 from .export import save_image_rgb
 from .mesh_render import interpolate, rasterize
 from .template import load_obj_uv  # noqa: F401  (re-exported)
@@ -63,23 +63,8 @@ def grid_atlas(num_faces: int, resolution: int, gutter: int = 1) -> Tuple[np.nda
     return vt, np.arange(3 * F, dtype=np.int32).reshape(F, 3)
 
 
-def _check(ret: int, what: str) -> None:
-    if ret < 0:
-        raise RuntimeError(f"{what} failed ({ret}): {_native.lib().gd_bake_last_error().decode('utf-8', 'replace')}")
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _gpu(name: str, what: str, t) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the HIP kernels have no CPU path ({what} must be on the GPU)")
-    return t
-
-
 def _mask_u8(name: str, mask) -> torch.Tensor:
-    _gpu(name, "mask", mask)
+    require_gpu(name, "mask", mask)
     if mask.dim() != 2:
         raise ValueError(f"{name}: mask must be [H,W]")
     if mask.dtype == torch.bool:
@@ -96,17 +81,15 @@ def uv_padding_index(mask: torch.Tensor, padding: int) -> torch.Tensor:
     m = _mask_u8("uv_padding_index", mask)
     H, W = m.shape
     src = torch.empty((H, W), dtype=torch.int32, device=m.device)
-    with torch.cuda.device(m.device):
-        _check(_native.lib().gd_bake_pad_index(_stream(m.device), H, W, int(padding), m.data_ptr(), src.data_ptr()),
-               "gd_bake_pad_index")
+    launch("gd_bake_pad_index", m.device, H, W, int(padding), m, src)
     return src
 
 
 def resolve_u8(image: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     """uint8 [H,W,C]: ``(uint8)(int)(clamp(image[src], 0, 1) * 255)`` where ``src >= 0``, 0 elsewhere (NaN gives 0).
     ``image``: float32 [H,W,C], C <= 4; ``src``: int32 [H,W]."""
-    _gpu("resolve_u8", "image", image)
-    _gpu("resolve_u8", "src", src)
+    require_gpu("resolve_u8", "image", image)
+    require_gpu("resolve_u8", "src", src)
     if image.dtype != torch.float32 or src.dtype != torch.int32:
         raise TypeError("resolve_u8: image must be float32 and src int32")
     if image.dim() != 3 or src.dim() != 2 or tuple(image.shape[:2]) != tuple(src.shape) or image.device != src.device:
@@ -114,16 +97,14 @@ def resolve_u8(image: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     H, W, C = image.shape
     img, s = image.detach().contiguous(), src.contiguous()
     out = torch.empty((H, W, C), dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        _check(_native.lib().gd_bake_resolve_u8(_stream(img.device), H, W, C, img.data_ptr(), s.data_ptr(),
-                                                out.data_ptr()), "gd_bake_resolve_u8")
+    launch("gd_bake_resolve_u8", img.device, H, W, C, img, s, out)
     return out
 
 
 def uv_padding(image: torch.Tensor, mask: torch.Tensor, padding: int) -> torch.Tensor:
     """kiui's ``uv_padding(image, mask, padding)`` with the tie rule of include/gd_bake.h, quantised: uint8 [H,W,C] in which
     every texel within L1 distance ``padding`` of the mask holds its nearest covered texel's colour and the rest is 0."""
-    _gpu("uv_padding", "image", image)
+    require_gpu("uv_padding", "image", image)
     return resolve_u8(image, uv_padding_index(mask, padding))
 
 
@@ -135,8 +116,8 @@ def bake_texture(field, v: torch.Tensor, f: torch.Tensor, vt, ft, resolution: in
     on the device of ``v``.  The atlas is rasterized as the triangles (2u - 1, 2v - 1, 0, 1), positions are interpolated
     with the atlas's barycentrics over ``f``, the field is asked once for the whole atlas with the coverage as its mask,
     and the charts are padded by ``padding`` texels (``uv_padding``)."""
-    _gpu("bake_texture", "v", v)
-    _gpu("bake_texture", "f", f)
+    require_gpu("bake_texture", "v", v)
+    require_gpu("bake_texture", "f", f)
     dev = v.device
     H = W = int(resolution)
     vt = torch.as_tensor(np.asarray(vt) if not isinstance(vt, torch.Tensor) else vt).to(dev, torch.float32)

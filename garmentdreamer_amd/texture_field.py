@@ -30,7 +30,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native
-from .mesh_render import MeshRenderer, antialias, antialias_weights, interpolate, rasterize, safe_normalize
+from ._launch import launch, require_gpu, scratch
+from .flat_adam import padded, reseat
+from .mesh_render import MeshRenderer
 
 FEATURES = 2
 FIELD_WIDTH = 32
@@ -92,33 +94,15 @@ def grid_layout(num_levels: int = 16, base_resolution: int = 16, per_level_scale
     return GridLayout(num_levels, scale, res, size, offset, res ** 3 <= size)
 
 
-def _check(ret: int, what: str) -> None:
-    if ret < 0:
-        raise RuntimeError(f"{what} failed ({ret}): {_native.lib().gd_texture_last_error().decode('utf-8', 'replace')}")
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _gpu(name: str, what: str, t, dtype) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: the HIP kernels have no CPU path ({what} must be on the GPU)")
-    if t.dtype != dtype:
-        raise TypeError(f"{name}: {what} must be {dtype}")
-    return t
-
-
 def _points(name: str, x, mask):
     """(x [N,3] contiguous and detached, mask uint8 [N] or None)"""
-    _gpu(name, "x", x, torch.float32)
+    require_gpu(name, "x", x, torch.float32)
     if x.dim() != 2 or x.shape[1] != 3:
         raise ValueError(f"{name}: x must be [N,3]")
     if x.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError(f"{name}: " + _X_GRAD)
     if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise RuntimeError(f"{name}: the HIP kernels have no CPU path (mask must be on the GPU)")
+        require_gpu(name, "mask", mask)
         if mask.numel() != x.shape[0]:
             raise ValueError(f"{name}: mask must have one element per point")
         mask = mask.reshape(-1)
@@ -128,10 +112,6 @@ def _points(name: str, x, mask):
             raise TypeError(f"{name}: mask must be bool or uint8")
         mask = mask.contiguous()
     return x.detach().contiguous(), mask
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 def _sinks(params):
@@ -154,41 +134,27 @@ def _grad_targets(params, sinks):
 class _Encode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, grid, layout, struct):
-        dev = x.device
-        enc = torch.empty((x.shape[0], layout.output_dim), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_texture_encode_forward(_stream(dev), x.shape[0], x.data_ptr(), _ptr(mask),
-                                                           grid.data_ptr(), struct, enc.data_ptr()),
-                   "gd_texture_encode_forward")
-        ctx.save_for_backward(x, mask if mask is not None else x.new_empty(0), grid)
-        ctx.has_mask, ctx.struct, ctx.sinks = mask is not None, struct, _sinks([grid])
+        enc = torch.empty((x.shape[0], layout.output_dim), dtype=torch.float32, device=x.device)
+        launch("gd_texture_encode_forward", x.device, x.shape[0], x, mask, grid, struct, enc)
+        ctx.save_for_backward(x, mask, grid)
+        ctx.struct, ctx.sinks = struct, _sinks([grid])
         return enc
 
     @staticmethod
     def backward(ctx, denc):
         x, mask, grid = ctx.saved_tensors
-        dev = x.device
-        denc = denc.contiguous()
         (buf, ret), = _grad_targets([grid], ctx.sinks)
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_texture_encode_backward(_stream(dev), x.shape[0], x.data_ptr(),
-                                                            mask.data_ptr() if ctx.has_mask else None, denc.data_ptr(),
-                                                            ctx.struct, buf.data_ptr()), "gd_texture_encode_backward")
+        launch("gd_texture_encode_backward", x.device, x.shape[0], x, mask, denc.contiguous(), ctx.struct, buf)
         return None, None, ret, None, None
 
 
 class _Field(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, grid, w1, b1, w2, b2, struct):
-        dev = x.device
-        color = torch.empty((x.shape[0], 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _check(_native.lib().gd_texture_field_forward(_stream(dev), x.shape[0], x.data_ptr(), _ptr(mask),
-                                                          grid.data_ptr(), struct, w1.data_ptr(), b1.data_ptr(),
-                                                          w2.data_ptr(), b2.data_ptr(), color.data_ptr()),
-                   "gd_texture_field_forward")
-        ctx.save_for_backward(x, mask if mask is not None else x.new_empty(0), grid, w1, b1, w2, b2, color)
-        ctx.has_mask, ctx.struct, ctx.sinks = mask is not None, struct, _sinks([grid, w1, b1, w2, b2])
+        color = torch.empty((x.shape[0], 3), dtype=torch.float32, device=x.device)
+        launch("gd_texture_field_forward", x.device, x.shape[0], x, mask, grid, struct, w1, b1, w2, b2, color)
+        ctx.save_for_backward(x, mask, grid, w1, b1, w2, b2, color)
+        ctx.struct, ctx.sinks = struct, _sinks([grid, w1, b1, w2, b2])
         return color
 
     @staticmethod
@@ -196,21 +162,15 @@ class _Field(torch.autograd.Function):
         x, mask, grid, w1, b1, w2, b2, color = ctx.saved_tensors
         dev = x.device
         n = x.shape[0]
-        L = _native.lib()
         dcolor = dcolor.contiguous()
         targets = _grad_targets([grid, w1, b1, w2, b2], ctx.sinks)
-        scratch = torch.empty(max(L.gd_texture_field_backward_scratch_bytes(n), 1), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _check(L.gd_texture_field_backward(_stream(dev), n, x.data_ptr(), mask.data_ptr() if ctx.has_mask else None,
-                                               grid.data_ptr(), ctx.struct, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                               b2.data_ptr(), color.data_ptr(), dcolor.data_ptr(),
-                                               *[t[0].data_ptr() for t in targets], scratch.data_ptr()),
-                   "gd_texture_field_backward")
+        launch("gd_texture_field_backward", dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
+               *[t[0] for t in targets], scratch(_native.lib().gd_texture_field_backward_scratch_bytes(n), dev))
         return (None, None) + tuple(t[1] for t in targets) + (None,)
 
 
 def _param(name: str, what: str, p: torch.Tensor, shape) -> torch.Tensor:
-    _gpu(name, what, p, torch.float32)
+    require_gpu(name, what, p, torch.float32)
     if tuple(p.shape) != tuple(shape) or not p.is_contiguous():
         raise ValueError(f"{name}: {what} must be a contiguous {tuple(shape)} tensor")
     return p
@@ -365,27 +325,9 @@ class TextureFieldOptimizer:
         grid = [field_module.encoder.params]
         mlp = list(field_module.mlp.parameters())
         for p in grid + mlp:
-            _gpu("TextureFieldOptimizer", "every parameter", p, torch.float32)
-        dev = grid[0].device
-        pad = lambda k: (k + 63) // 64 * 64          # every view starts 256-byte aligned
-        n_grid = pad(grid[0].numel())
-        n = n_grid + sum(pad(p.numel()) for p in mlp)
-        self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._grad = torch.zeros(n, dtype=torch.float32, device=dev)          # padding stays 0: its update is 0 / (0 + eps)
-        self._exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
-        off = 0
-        with torch.no_grad():
-            for p in grid + mlp:
-                k = p.numel()
-                view = self._flat[off:off + k].view(p.shape)
-                view.copy_(p.data)
-                p.data = view
-                gview = self._grad[off:off + k].view(p.shape)
-                p.grad = gview
-                p._gd_grad_sink = gview
-                off += pad(k)
-        self._ends = (C.c_int64 * 2)(n_grid, n)
+            require_gpu("TextureFieldOptimizer", "every parameter", p, torch.float32)
+        self._flat, self._grad, self._exp_avg, self._exp_avg_sq, _ = reseat(grid + mlp)
+        self._ends = (C.c_int64 * 2)(padded(grid[0].numel()), self._flat.numel())
         self.param_groups = [{"params": grid, "lr": float(hashgrid_lr)}, {"params": mlp, "lr": float(mlp_lr)}]
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.step_count = 0
@@ -397,12 +339,8 @@ class TextureFieldOptimizer:
     def step(self):
         self.step_count += 1
         lrs = (C.c_double * 2)(float(self.param_groups[0]["lr"]), float(self.param_groups[1]["lr"]))
-        dev = self._flat.device
-        with torch.cuda.device(dev):
-            _native.check_scene(_native.lib().gd_scene_adam_step(
-                _stream(dev), self._flat.data_ptr(), self._grad.data_ptr(), self._exp_avg.data_ptr(),
-                self._exp_avg_sq.data_ptr(), self._flat.numel(), 2, self._ends, lrs, self.betas[0], self.betas[1],
-                self.eps, self.step_count), "gd_scene_adam_step")
+        launch("gd_scene_adam_step", self._flat.device, self._flat, self._grad, self._exp_avg, self._exp_avg_sq,
+               self._flat.numel(), 2, self._ends, lrs, self.betas[0], self.betas[1], self.eps, self.step_count)
 
 
 class NeTFRenderer(MeshRenderer):
@@ -415,7 +353,7 @@ class NeTFRenderer(MeshRenderer):
     mode sees torch's own synchronisation points, not a wait inside the solver library behind ``inv_ex``, which is not
     excluded by it.  A singular or non-finite pose raises, as in ``MeshRenderer``; it is detected on the host."""
 
-    def _upload(self, pose, proj):
+    def _matrices(self, pose, proj):
         """device float32 [3,4,4]: inverse pose, projection, pose"""
         pose = np.asarray(pose).astype(np.float32)
         try:
@@ -428,12 +366,8 @@ class NeTFRenderer(MeshRenderer):
         mats = torch.from_numpy(mats).pin_memory().to(self.v.device, non_blocking=True)
         return torch.stack([torch.linalg.inv_ex(mats[0]).inverse, mats[1], mats[0]])
 
-    def _clip(self, mats):
-        v_cam = torch.matmul(F.pad(self.v, pad=(0, 1), mode="constant", value=1.0), mats[0].T).float()
-        return v_cam, (v_cam @ mats[1].T).contiguous()
-
-    def clip_positions(self, pose, proj):
-        return self._clip(self._upload(pose, proj))
+    def _texture(self, xyzs, mask):
+        return self.texture_fn(xyzs, mask).float()
 
     def export_mesh(self, save_path, texture_resolution=2048, padding=16, reverse=False, vt=None, ft=None):
         """``Renderer.export_mesh`` (mesh_renderer.py:260-313) plus optional UVs: bakes ``texture_fn`` into the atlas ``vt`` /
@@ -442,32 +376,3 @@ class NeTFRenderer(MeshRenderer):
         from . import texture_bake
         return texture_bake.export_textured_mesh(save_path, self.texture_fn, self.v, self.f, texture_resolution, padding,
                                                  reverse, vt, ft)
-
-    def render(self, pose, proj, h0, w0, ssaa=1, bg_color=1):
-        if ssaa != 1:
-            raise ValueError("NeTFRenderer.render: ssaa != 1 is not implemented (the reference's trainer passes 1)")
-        h, w = int(h0), int(w0)
-        v, f, topo = self.v, self.f, self.topology
-        mats = self._upload(pose, proj)
-        v_cam, v_clip = self._clip(mats)
-
-        rast = rasterize(v_clip, f, (h, w))
-        wts = antialias_weights(rast, v_clip, f, topo)
-
-        alpha = torch.clamp(rast[..., -1:], 0, 1).contiguous()
-        alpha = antialias(alpha, rast, v_clip, f, weights=wts).clamp(0, 1)
-        depth = interpolate(-v_cam[..., 2:3].contiguous(), rast, f)     # a slice: a list index would upload its indices
-        xyzs_ = interpolate(v, rast, f)
-        mask = (alpha > 0).view(-1)
-        color = self.texture_fn(xyzs_.view(-1, 3), mask).float().view(h, w, 3)
-        color = antialias(color, rast, v_clip, f, weights=wts).clamp(0, 1)
-        color = alpha * color + (1 - alpha) * bg_color
-
-        normal_ = interpolate(self.vn, rast, f)
-        normal = safe_normalize(normal_)
-        with torch.no_grad():
-            position = antialias(xyzs_, rast, v_clip, f, weights=wts)
-            normal_aa = antialias(normal_, rast, v_clip, f, weights=wts)
-            view_direction = F.normalize(position - mats[2][:3, 3], dim=-1)
-            cosines_view = F.cosine_similarity(view_direction, normal_aa, dim=-1, eps=1e-6)
-        return {"image": color, "alpha": alpha, "depth": depth, "normal": (normal + 1) / 2, "cosinesview": cosines_view}

@@ -251,6 +251,37 @@ def test_backwards_are_bit_reproducible():
     assert np.abs(g[..., :2] - want).max() <= 1e-5                       # three products of values <= 2 in fp32
 
 
+def test_both_modules_give_bit_equal_gradients_where_both_have_one():
+    """``mesh_render`` and ``mesh_deform`` are two policies over the same ops: with the same attr / colour, upstream
+    gradient, rast, pos and topology, the gradient to ``attr`` of ``interpolate`` and, with ``pos`` detached, the gradient
+    to ``color`` of ``antialias`` are the same bits.  Neither backward uses atomics, so no tolerance is involved."""
+    from garmentdreamer_amd import mesh_deform as md
+    from garmentdreamer_amd import mesh_render as mr
+    pos, tri, topo = _gpu_scene("edge")
+    rast = mr.rasterize(pos, tri, (H, W))
+    rng = np.random.RandomState(40)
+
+    def grad_of(op, x, dout):
+        x = x.clone().requires_grad_(True)
+        op(x).backward(dout)
+        return x.grad
+
+    for C in (1, 3, 8):
+        attr = _dev(rng.uniform(-1, 1, size=(pos.shape[0], C)).astype(np.float32))
+        dout = _dev(rng.uniform(-1, 1, size=(H, W, C)).astype(np.float32))
+        fixed = grad_of(lambda a: mr.interpolate(a, rast, tri, pos=pos, topology=topo), attr, dout)
+        moving = grad_of(lambda a: md.interpolate(a, rast, tri, pos, topo), attr, dout)
+        assert tuple(fixed.shape) == (pos.shape[0], C) and fixed.abs().max() > 0, C
+        assert torch.equal(fixed.view(torch.int32), moving.view(torch.int32)), C
+    for C in (1, 3):
+        color = _dev(rng.uniform(0, 1, size=(H, W, C)).astype(np.float32))
+        dout = _dev(rng.uniform(-1, 1, size=(H, W, C)).astype(np.float32))
+        fixed = grad_of(lambda c: mr.antialias(c, rast, pos, tri, topology=topo), color, dout)
+        moving = grad_of(lambda c: md.antialias(c, rast, pos.detach(), tri, topo), color, dout)
+        assert fixed.abs().max() > 0 and not torch.equal(fixed, dout), C      # the blend did something
+        assert torch.equal(fixed.view(torch.int32), moving.view(torch.int32)), C
+
+
 def test_visible_vertices():
     from garmentdreamer_amd import mesh_deform as md
     s = _scene("edge")
