@@ -156,6 +156,16 @@ TEXTURE_SIGNATURES = {
     "gd_texture_last_error": (C.c_char_p, []),
 }
 
+# its opt-in reproducible grid gradient: dgrid by stable sort and sum (include/gd_texture_sorted.h); messages go through
+# gd_texture_last_error
+TEXTURE_SORTED_MAX_POINTS = 1 << 24
+TEXTURE_SORTED_SIGNATURES = {
+    "gd_texture_sorted_scratch_bytes": (C.c_size_t, [_i, TextureLayout]),
+    "gd_texture_encode_backward_sorted": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout, _vp, _vp]),  # ..., denc, layout, dgrid scratch
+    "gd_texture_field_backward_sorted": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout] + [_vp] * 14),  # as field_backward up to
+                                                                                    # db2, then denc slab_scratch sort_scratch
+}
+
 # the texture bake's padding: nearest covered texel and the 8-bit gather (include/gd_bake.h)
 BAKE_MAX_PADDING = 64
 BAKE_MAX_CHANNELS = 4
@@ -193,7 +203,8 @@ def lib():
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
-                + list(TEXTURE_SIGNATURES.items()) + list(BAKE_SIGNATURES.items()):
+                + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
+                + list(BAKE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

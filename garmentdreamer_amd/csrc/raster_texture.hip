@@ -15,13 +15,18 @@
 //                               chunks blockIdx, blockIdx + gridDim, ... and keeps its sums in registers; it writes ONE
 //                               slab row at the end.  slab_sum_kernel adds the rows in ascending order to the
 //                               destinations: no float atomics on the MLP gradients, reruns bit-identical.
-//   dgrid                       plain atomics; its last bits depend on arrival order (stated in the header).
+//   dgrid                       plain atomics; its last bits depend on arrival order (stated in the header).  The opt-in
+//                               reproducible form (include/gd_texture_sorted.h) has its entries here and its kernels in
+//                               raster_texture_sorted.hip; its fused variant is field_backward_kernel<true>, which stores
+//                               denc [N][32] instead of scattering it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/gd_texture.h"
+#include "../../include/gd_texture_sorted.h"
+#include "raster_texture_cells.h"
 
 namespace gd {
 namespace {
@@ -43,62 +48,6 @@ constexpr int kBwdThreads = 128;      // points per pass of a backward workgroup
 constexpr int kRowStride = 36;        // floats per point in the LDS images of enc and h: rows stay 16-byte aligned
 constexpr int kMaxSlabRows = 1024;
 constexpr int kSumCols = 16, kSumGroups = 16;
-
-struct Level {
-    float scale;
-    uint32_t res, size, offset;
-    bool dense, pow2;
-};
-
-__device__ __forceinline__ Level level_of(const gd_texture_layout& lay, int l)
-{
-    Level v;
-    v.scale = lay.scale[l];
-    v.res = (uint32_t)lay.res[l];
-    v.size = (uint32_t)lay.size[l];
-    v.offset = (uint32_t)lay.offset[l];
-    v.dense = (uint64_t)v.res * v.res * v.res <= (uint64_t)v.size;
-    v.pow2 = (v.size & (v.size - 1)) == 0;
-    return v;
-}
-
-struct Cell {
-    uint32_t c[3];
-    float w[3];
-};
-
-__device__ __forceinline__ Cell cell_of(const float u[3], float scale)
-{
-    Cell ce;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        float p = scale * u[d];
-        p = p + 0.5f;
-        const float fl = floorf(p);
-        ce.c[d] = (uint32_t)(int32_t)fl;
-        ce.w[d] = p - fl;
-    }
-    return ce;
-}
-
-// always < lv.size
-__device__ __forceinline__ uint32_t corner_index(const Level& lv, const Cell& ce, int i)
-{
-    const uint32_t g0 = ce.c[0] + (uint32_t)(i & 1), g1 = ce.c[1] + (uint32_t)((i >> 1) & 1),
-                   g2 = ce.c[2] + (uint32_t)((i >> 2) & 1);
-    const uint32_t idx = lv.dense ? g0 + g1 * lv.res + g2 * lv.res * lv.res
-                                  : g0 ^ (g1 * 2654435761u) ^ (g2 * 805459861u);
-    if (lv.pow2) return idx & (lv.size - 1);
-    return idx < lv.size ? idx : idx % lv.size;
-}
-
-__device__ __forceinline__ float corner_weight(const Cell& ce, int i)
-{
-    const float a = (i & 1) ? ce.w[0] : 1.0f - ce.w[0];
-    const float b = (i & 2) ? ce.w[1] : 1.0f - ce.w[1];
-    const float c = (i & 4) ? ce.w[2] : 1.0f - ce.w[2];
-    return (a * b) * c;
-}
 
 __device__ __forceinline__ float2 encode_level(const float2* __restrict__ grid, const Level& lv, const float u[3])
 {
@@ -125,20 +74,6 @@ __device__ __forceinline__ void scatter_level(float* __restrict__ dgrid, const L
         atomicAdd(dst, w * d0);
         atomicAdd(dst + 1, w * d1);
     }
-}
-
-// the point's u, or false for a point that takes no part (beyond N, masked out, or a non-finite coordinate)
-__device__ __forceinline__ bool load_point(int n, int N, const float* __restrict__ x, const uint8_t* __restrict__ mask,
-                                           float u[3])
-{
-    if (n >= N) return false;
-    if (mask && mask[n] == 0) return false;
-    const float x0 = x[3 * (size_t)n], x1 = x[3 * (size_t)n + 1], x2 = x[3 * (size_t)n + 2];
-    if (!(__builtin_isfinite(x0) && __builtin_isfinite(x1) && __builtin_isfinite(x2))) return false;
-    u[0] = (x0 + 1.0f) * 0.5f;
-    u[1] = (x1 + 1.0f) * 0.5f;
-    u[2] = (x2 + 1.0f) * 0.5f;
-    return true;
 }
 
 // ---- the encoding on its own ---------------------------------------------------------------------------------------------
@@ -243,6 +178,10 @@ __global__ __launch_bounds__(256) void field_forward_kernel(int N, const float* 
     for (int c = 0; c < 3; c++) color[3 * (size_t)n + c] = o[c];
 }
 
+// kStoreDenc = false: denc is scattered into dgrid with atomics.  kStoreDenc = true (the sorted path): dgrid is not touched
+// and the point's row of denc [N][32] is stored instead, zeros for a point that takes no part; the same parameter carries
+// either pointer, so that the atomic instantiation keeps its signature and its code.
+template <bool kStoreDenc>
 __global__ __launch_bounds__(kBwdThreads) void field_backward_kernel(
     int N, int nchunks, const float* __restrict__ x, const uint8_t* __restrict__ mask, const float2* __restrict__ grid,
     gd_texture_layout lay, const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
@@ -294,10 +233,24 @@ __global__ __launch_bounds__(kBwdThreads) void field_backward_kernel(
 #pragma unroll
                 for (int k = 0; k < kWidth; k++) denc[k] = __builtin_fmaf(mlp[kW1 + j * kWidth + k], dh, denc[k]);
             }
+            if constexpr (kStoreDenc) {
+                float4* row = reinterpret_cast<float4*>(dgrid + (size_t)n * kWidth);
 #pragma unroll
-            for (int l = 0; l < kLevels; l++) scatter_level(dgrid, level_of(lay, l), u, denc[2 * l], denc[2 * l + 1]);
+                for (int k = 0; k < kWidth / 4; k++)
+                    row[k] = make_float4(denc[4 * k], denc[4 * k + 1], denc[4 * k + 2], denc[4 * k + 3]);
+            } else {
+#pragma unroll
+                for (int l = 0; l < kLevels; l++) scatter_level(dgrid, level_of(lay, l), u, denc[2 * l], denc[2 * l + 1]);
+            }
         } else {
             for (int j = 0; j < kWidth; j++) hS[t * kRowStride + j] = 0.0f;
+            if constexpr (kStoreDenc) {
+                if (n < N) {
+                    float4* row = reinterpret_cast<float4*>(dgrid + (size_t)n * kWidth);
+#pragma unroll
+                    for (int k = 0; k < kWidth / 4; k++) row[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                }
+            }
         }
         __syncthreads();
 
@@ -417,6 +370,15 @@ int launched(const char* what)
     return 0;
 }
 
+int need_sorted_points(const char* what, int N)
+{
+    if (N <= kSortedMaxPoints) return 0;
+    char buf[200];
+    snprintf(buf, sizeof(buf), "%s: N must be in 0..2^24 (item ids and scratch grow with N): use the atomic path or split "
+             "the batch", what);
+    return tfail(-1, buf);
+}
+
 dim3 grid_of(int n, int per) { return dim3((unsigned)(((int64_t)n + per - 1) / per)); }
 
 int backward_chunks(int N) { return (int)(((int64_t)N + kBwdThreads - 1) / kBwdThreads); }
@@ -482,11 +444,56 @@ int gd_texture_field_backward(void* stream, int N, const float* x, const uint8_t
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int rows = backward_rows(N);
-    hipLaunchKernelGGL(field_backward_kernel, dim3((unsigned)rows), dim3(kBwdThreads), 0, s, N, backward_chunks(N), x,
-                       mask, (const float2*)grid, layout, w1, b1, w2, b2, color, dcolor, dgrid, (float*)scratch);
+    hipLaunchKernelGGL(field_backward_kernel<false>, dim3((unsigned)rows), dim3(kBwdThreads), 0, s, N, backward_chunks(N),
+                       x, mask, (const float2*)grid, layout, w1, b1, w2, b2, color, dcolor, dgrid, (float*)scratch);
     hipLaunchKernelGGL(slab_sum_kernel, grid_of(kMlpFloats, kSumCols), dim3(kSumCols * kSumGroups), 0, s, rows,
                        (const float*)scratch, dw1, db1, dw2, db2);
     return launched("field backward");
+}
+
+// ---- dgrid by stable sort and sum (include/gd_texture_sorted.h; the kernels: raster_texture_sorted.hip) --------------------
+
+size_t gd_texture_sorted_scratch_bytes(int N, gd_texture_layout layout)
+{
+    if (N <= 0 || gd::layout_error(layout)) return 0;      // (defined above 2^24 too: non-decreasing in N)
+    return gd::sorted_dgrid_scratch_bytes(N, layout);
+}
+
+int gd_texture_encode_backward_sorted(void* stream, int N, const float* x, const uint8_t* mask, const float* denc,
+                                      gd_texture_layout layout, float* dgrid, void* scratch)
+{
+    using namespace gd;
+    const char* what = "encode backward sorted";
+    if (int r = check_common(what, N, layout, !x || !denc || !dgrid || !scratch, nullptr)) return r;
+    if (int r = need_sorted_points(what, N)) return r;
+    if (N == 0) return 0;
+    launch_sorted_dgrid((hipStream_t)stream, N, x, mask, denc, layout, dgrid, scratch);
+    return launched(what);
+}
+
+int gd_texture_field_backward_sorted(void* stream, int N, const float* x, const uint8_t* mask, const float* grid,
+                                     gd_texture_layout layout, const float* w1, const float* b1, const float* w2,
+                                     const float* b2, const float* color, const float* dcolor, float* dgrid, float* dw1,
+                                     float* db1, float* dw2, float* db2, float* denc, void* slab_scratch,
+                                     void* sort_scratch)
+{
+    using namespace gd;
+    const char* what = "field backward sorted";
+    const bool nulls = !x || !grid || !w1 || !b1 || !w2 || !b2 || !color || !dcolor || !dgrid || !dw1 || !db1 || !dw2 ||
+                       !db2 || !denc || !slab_scratch || !sort_scratch;
+    if (int r = check_common(what, N, layout, nulls, grid)) return r;
+    if (int r = need_field_width(what, layout)) return r;
+    if (int r = need_sorted_points(what, N)) return r;
+    if ((uintptr_t)denc & 15) return tfail(-1, "field backward sorted: denc must be 16-byte aligned");
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = backward_rows(N);
+    hipLaunchKernelGGL(field_backward_kernel<true>, dim3((unsigned)rows), dim3(kBwdThreads), 0, s, N, backward_chunks(N),
+                       x, mask, (const float2*)grid, layout, w1, b1, w2, b2, color, dcolor, denc, (float*)slab_scratch);
+    hipLaunchKernelGGL(slab_sum_kernel, grid_of(kMlpFloats, kSumCols), dim3(kSumCols * kSumGroups), 0, s, rows,
+                       (const float*)slab_scratch, dw1, db1, dw2, db2);
+    launch_sorted_dgrid(s, N, x, mask, denc, layout, dgrid, sort_scratch);
+    return launched(what);
 }
 
 const char* gd_texture_last_error(void) { return gd::g_texture_err; }

@@ -16,8 +16,14 @@ Gradients follow ``.grad`` semantics at the C level (every kernel ADDS into the 
 ``TextureFieldOptimizer`` has re-seated carries ``_gd_grad_sink`` (a view of the optimizer's flat gradient buffer, as
 ``flat_adam.FlatAdam`` gives the LoRA adapters): the backward adds straight into it and returns nothing to autograd.
 Without a sink the backward allocates a zeroed gradient and returns it.  There is no gradient to ``x``: the live
-configuration has ``fix_geo: true``; ``x.requires_grad`` raises.  The gradient to the grid is accumulated with float
-atomics (as tiny-cuda-nn does): its last bits differ between runs; the MLP gradients and every forward are reproducible.
+configuration has ``fix_geo: true``; ``x.requires_grad`` raises.
+
+Determinism.  Every forward and the MLP gradients are bit-reproducible.  The gradient to the grid is by default accumulated
+with float atomics (as tiny-cuda-nn does): its last bits differ between runs.  ``deterministic=True`` (``encode``, ``field``,
+``HashGridEncoder``, ``TextureField``) routes the backward through the sorted path of include/gd_texture_sorted.h instead: a
+stable sort of the contributions by grid entry and one sequential sum per entry in ascending (point, corner) order, no float
+atomics; the grid gradient is then a pure function of the inputs, and two runs from the same seed stay bit-equal.  The
+forwards are the same either way; the path needs ``N <= 2^24`` points per call and scratch that grows with N.
 """
 from __future__ import annotations
 
@@ -131,30 +137,42 @@ def _grad_targets(params, sinks):
     return out
 
 
+def _sort_scratch(n: int, struct, dev) -> torch.Tensor:
+    """the sorted path's scratch; more than 2^24 points are refused here, before anything of that size is allocated"""
+    if n > _native.TEXTURE_SORTED_MAX_POINTS:
+        raise ValueError(f"deterministic=True takes at most 2^24 points per call ({n} given): use the atomic path or split "
+                         "the batch")
+    return scratch(_native.lib().gd_texture_sorted_scratch_bytes(n, struct), dev)
+
+
 class _Encode(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mask, grid, layout, struct):
+    def forward(ctx, x, mask, grid, layout, struct, deterministic):
         enc = torch.empty((x.shape[0], layout.output_dim), dtype=torch.float32, device=x.device)
         launch("gd_texture_encode_forward", x.device, x.shape[0], x, mask, grid, struct, enc)
         ctx.save_for_backward(x, mask, grid)
-        ctx.struct, ctx.sinks = struct, _sinks([grid])
+        ctx.struct, ctx.sinks, ctx.deterministic = struct, _sinks([grid]), deterministic
         return enc
 
     @staticmethod
     def backward(ctx, denc):
         x, mask, grid = ctx.saved_tensors
         (buf, ret), = _grad_targets([grid], ctx.sinks)
-        launch("gd_texture_encode_backward", x.device, x.shape[0], x, mask, denc.contiguous(), ctx.struct, buf)
-        return None, None, ret, None, None
+        if ctx.deterministic:
+            launch("gd_texture_encode_backward_sorted", x.device, x.shape[0], x, mask, denc.contiguous(), ctx.struct, buf,
+                   _sort_scratch(x.shape[0], ctx.struct, x.device))
+        else:
+            launch("gd_texture_encode_backward", x.device, x.shape[0], x, mask, denc.contiguous(), ctx.struct, buf)
+        return None, None, ret, None, None, None
 
 
 class _Field(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mask, grid, w1, b1, w2, b2, struct):
+    def forward(ctx, x, mask, grid, w1, b1, w2, b2, struct, deterministic):
         color = torch.empty((x.shape[0], 3), dtype=torch.float32, device=x.device)
         launch("gd_texture_field_forward", x.device, x.shape[0], x, mask, grid, struct, w1, b1, w2, b2, color)
         ctx.save_for_backward(x, mask, grid, w1, b1, w2, b2, color)
-        ctx.struct, ctx.sinks = struct, _sinks([grid, w1, b1, w2, b2])
+        ctx.struct, ctx.sinks, ctx.deterministic = struct, _sinks([grid, w1, b1, w2, b2]), deterministic
         return color
 
     @staticmethod
@@ -164,9 +182,15 @@ class _Field(torch.autograd.Function):
         n = x.shape[0]
         dcolor = dcolor.contiguous()
         targets = _grad_targets([grid, w1, b1, w2, b2], ctx.sinks)
-        launch("gd_texture_field_backward", dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
-               *[t[0] for t in targets], scratch(_native.lib().gd_texture_field_backward_scratch_bytes(n), dev))
-        return (None, None) + tuple(t[1] for t in targets) + (None,)
+        slab = scratch(_native.lib().gd_texture_field_backward_scratch_bytes(n), dev)
+        if ctx.deterministic:
+            denc = torch.empty((n, FIELD_WIDTH), dtype=torch.float32, device=dev)
+            launch("gd_texture_field_backward_sorted", dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
+                   *[t[0] for t in targets], denc, slab, _sort_scratch(n, ctx.struct, dev))
+        else:
+            launch("gd_texture_field_backward", dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
+                   *[t[0] for t in targets], slab)
+        return (None, None) + tuple(t[1] for t in targets) + (None, None)
 
 
 def _param(name: str, what: str, p: torch.Tensor, shape) -> torch.Tensor:
@@ -176,17 +200,20 @@ def _param(name: str, what: str, p: torch.Tensor, shape) -> torch.Tensor:
     return p
 
 
-def encode(x: torch.Tensor, grid: torch.Tensor, layout: GridLayout, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+def encode(x: torch.Tensor, grid: torch.Tensor, layout: GridLayout, mask: Optional[torch.Tensor] = None,
+           deterministic: bool = False) -> torch.Tensor:
     """``enc`` float32 [N, L F] of the points ``x`` [N,3] (in [-1, 1]^3; anything finite is defined) in the flat table
-    ``grid``; rows with ``mask == 0`` or a non-finite coordinate are 0 and pass no gradient."""
+    ``grid``; rows with ``mask == 0`` or a non-finite coordinate are 0 and pass no gradient.  ``deterministic``: the
+    gradient to ``grid`` by sort and sum instead of atomics (see the module's docstring)."""
     _param("encode", "grid", grid, (layout.num_params,))
     x, mask = _points("encode", x, mask)
-    return _Encode.apply(x, mask, grid, layout, layout.struct())
+    return _Encode.apply(x, mask, grid, layout, layout.struct(), bool(deterministic))
 
 
 def field(x: torch.Tensor, grid: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
-          layout: GridLayout, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``color`` float32 [N,3] = sigmoid(W2 relu(W1 enc + b1) + b2), one launch; needs ``L F = 32``."""
+          layout: GridLayout, mask: Optional[torch.Tensor] = None, deterministic: bool = False) -> torch.Tensor:
+    """``color`` float32 [N,3] = sigmoid(W2 relu(W1 enc + b1) + b2), one launch; needs ``L F = 32``.  ``deterministic``:
+    the gradient to ``grid`` by sort and sum instead of atomics (see the module's docstring)."""
     if layout.output_dim != FIELD_WIDTH:
         raise ValueError(f"field: the fused path needs num_levels * level_dim = {FIELD_WIDTH}")
     _param("field", "grid", grid, (layout.num_params,))
@@ -195,41 +222,46 @@ def field(x: torch.Tensor, grid: torch.Tensor, w1: torch.Tensor, b1: torch.Tenso
     _param("field", "w2", w2, (3, FIELD_WIDTH))
     _param("field", "b2", b2, (3,))
     x, mask = _points("field", x, mask)
-    return _Field.apply(x, mask, grid, w1, b1, w2, b2, layout.struct())
+    return _Field.apply(x, mask, grid, w1, b1, w2, b2, layout.struct(), bool(deterministic))
 
 
 class HashGridEncoder(nn.Module):
     """The reference's ``HashGridEncoder`` (texture_encoder.py:8-37): same signature, same ``per_level_scale``; ``params`` is
-    the flat table in tiny-cuda-nn's order (level, entry, feature), uniform in [-1e-4, 1e-4]."""
+    the flat table in tiny-cuda-nn's order (level, entry, feature), uniform in [-1e-4, 1e-4].  ``deterministic`` (kept as
+    ``.deterministic``): the gradient to ``params`` by sort and sum instead of atomics."""
 
     def __init__(self, input_dim=3, num_levels=16, level_dim=2, log2_hashmap_size=19, base_resolution=16,
-                 desired_resolution=1024, interpolation="linear", generator: Optional[torch.Generator] = None):
+                 desired_resolution=1024, interpolation="linear", generator: Optional[torch.Generator] = None,
+                 deterministic: bool = False):
         super().__init__()
         if input_dim != 3 or level_dim != FEATURES:
             raise NotImplementedError("HashGridEncoder: only input_dim=3 and level_dim=2 are built")
         if interpolation != "linear":
             raise NotImplementedError("HashGridEncoder: only linear interpolation is built (the reference never asks "
                                       "for smoothstep)")
-        self._set_layout(grid_layout(num_levels, base_resolution, None, log2_hashmap_size, desired_resolution), generator)
+        self._set_layout(grid_layout(num_levels, base_resolution, None, log2_hashmap_size, desired_resolution), generator,
+                         deterministic)
 
-    def _set_layout(self, layout: GridLayout, generator):
+    def _set_layout(self, layout: GridLayout, generator, deterministic=False):
         self.layout = layout
+        self.deterministic = bool(deterministic)
         self.input_dim = 3
         self.output_dim = layout.output_dim
         self.params = nn.Parameter((torch.rand(layout.num_params, generator=generator) * 2 - 1) * 1e-4)
 
     @classmethod
-    def from_layout(cls, layout: GridLayout, generator: Optional[torch.Generator] = None) -> "HashGridEncoder":
+    def from_layout(cls, layout: GridLayout, generator: Optional[torch.Generator] = None,
+                    deterministic: bool = False) -> "HashGridEncoder":
         """An encoder over any ``grid_layout(...)`` (the constructor's arguments cannot state ``per_level_scale``)."""
         self = cls.__new__(cls)
         nn.Module.__init__(self)
-        self._set_layout(layout, generator)
+        self._set_layout(layout, generator, deterministic)
         return self
 
     def forward(self, x, bound=1, mask=None):
         if bound != 1:
             raise ValueError("HashGridEncoder: only bound=1 is built")
-        return encode(x, self.params, self.layout, mask)
+        return encode(x, self.params, self.layout, mask, self.deterministic)
 
 
 WEIGHT_GRAD_BLOCK = 128
@@ -285,18 +317,23 @@ class AlbedoMLP(nn.Module):
 class TextureField(nn.Module):
     """``sigmoid(mlp(encoder(x)))`` in one launch forward, and one launch plus the fixed-order sum backward.
     ``encoder``: a ``HashGridEncoder`` with ``output_dim == 32`` (default: the reference's).  ``generator`` seeds the grid;
-    the MLP is ``nn.Linear``-initialised from torch's global generator."""
+    the MLP is ``nn.Linear``-initialised from torch's global generator.  ``deterministic``: if not ``None`` it is set on
+    the encoder; ``forward``, ``unfused`` and ``.encoder(...)`` all follow ``encoder.deterministic``."""
 
-    def __init__(self, encoder: Optional[HashGridEncoder] = None, generator: Optional[torch.Generator] = None):
+    def __init__(self, encoder: Optional[HashGridEncoder] = None, generator: Optional[torch.Generator] = None,
+                 deterministic: Optional[bool] = None):
         super().__init__()
         self.encoder = encoder if encoder is not None else HashGridEncoder(generator=generator)
+        if deterministic is not None:
+            self.encoder.deterministic = bool(deterministic)
         if self.encoder.output_dim != FIELD_WIDTH:
             raise ValueError(f"TextureField: the fused path needs an encoder with output_dim = {FIELD_WIDTH}")
         self.mlp = AlbedoMLP()
 
     def forward(self, x, mask=None):
         l1, l2 = self.mlp.net
-        return field(x, self.encoder.params, l1.weight, l1.bias, l2.weight, l2.bias, self.encoder.layout, mask)
+        return field(x, self.encoder.params, l1.weight, l1.bias, l2.weight, l2.bias, self.encoder.layout, mask,
+                     self.encoder.deterministic)
 
     def unfused(self, x, mask=None):
         """The same function through ``.encoder`` and ``.mlp`` (the [N,32] encoding goes through memory)."""

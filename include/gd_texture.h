@@ -51,7 +51,9 @@
  * DETERMINISM.  The forward is bit-reproducible.  The four MLP gradients are summed in a fixed order: a workgroup adds
  * its points in ascending order, writes one row of partials to the scratch slab, and one pass adds the rows in ascending
  * order to the destination; reruns are bit-identical.  dgrid is accumulated with no-return fp32 atomicAdd, as
- * tiny-cuda-nn does: its last bits depend on the order of arrival and differ from run to run.
+ * tiny-cuda-nn does: its last bits depend on the order of arrival and differ from run to run.  These entries stay as they
+ * are and stay the default; gd_texture_sorted.h declares the opt-in entries whose dgrid is a pure function of the inputs
+ * (a stable sort of the contributions by entry, then one sequential sum per entry in ascending (point, corner) order).
  */
 #ifndef GD_TEXTURE_H_INCLUDED
 #define GD_TEXTURE_H_INCLUDED
