@@ -551,24 +551,13 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
             a_reg[i] = __builtin_bit_cast(uint4, v);
         }
     };
-    const int cg = mean_rstd ? Cin / G : 1;
+    // GroupNorm: scale / shift of every channel of the tile's image, computed once into the table behind the stages
+    // (nn_device.h); the K loop reads the thread's octet of the chunk from there
+    const uint32_t tab_off = (uint32_t)(uintptr_t)(smem + 2 * kAStage + 2 * kBStage);
     auto storeA = [&](int buf, int c) {
-        char* dst = sA + buf * kAStage;
+        const uint32_t dst_off = (uint32_t)(uintptr_t)(sA + buf * kAStage);
         float sc[8], sh[8];
-        if (mean_rstd) {
-            const int ch0 = c * BK + a_chunk * 8;
-            const uint4 gq = *(const uint4*)(gamma + ch0), bq = *(const uint4*)(beta + ch0);
-            const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w}, bw[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int g = (ch0 + k) / cg;
-                const float2 mr = *(const float2*)(mean_rstd + ((size_t)nimg * G + g) * 2);
-                const float gm = bf2f((uint16_t)(gw[k >> 1] >> ((k & 1) * 16)));
-                const float bt = bf2f((uint16_t)(bw[k >> 1] >> ((k & 1) * 16)));
-                sc[k] = gm * mr.y;
-                sh[k] = bt - mr.x * sc[k];
-            }
-        }
+        if (mean_rstd) gn_table_read(tab_off, c * (BK / 8) + a_chunk, sc, sh);
 #pragma unroll
         for (int i = 0; i < NA; i++) {
             if (!((a_slot >> i) & 1u)) continue;
@@ -586,7 +575,11 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
                 }
                 v = make_uint4(w4[0], w4[1], w4[2], w4[3]);
             }
-            *(uint4*)(dst + a_lds[i]) = v;
+            // inline asm: the compiler cannot tell a plain LDS store from the target of the LDS-DMA in flight (the next
+            // weight slice) and would put s_waitcnt vmcnt(0) in front of it; the step's barrier waits for lgkmcnt(0) itself
+            typedef __attribute__((ext_vector_type(4))) uint32_t vec4;
+            const vec4 vv = {v.x, v.y, v.z, v.w};
+            asm volatile("ds_write_b128 %0, %1" ::"v"(dst_off + a_lds[i]), "v"(vv) : "memory");
         }
     };
 
@@ -644,8 +637,10 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
         }
     };
     if (GN) {
+        if (mean_rstd) gn_table_fill(tab_off, tid, THREADS, Cin, G, nimg, mean_rstd, gamma, beta);
         loadA(0);
         issueB(0, 0, 0);
+        if (mean_rstd) gn_table_sync();
         storeA(0, 0);
     } else {
         issueA(0, 0);
@@ -656,7 +651,9 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
         const char* pa = sA + (c & 1) * kAStage;
         for (int tap = 0; tap < 9; tap++, s++) {
             const int bufB = s & 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // (GN: the loader's asm LDS stores are not in the compiler's count)
+            if (GN) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (s + 1 < nsteps) issueB(bufB ^ 1, tap == 8 ? 0 : tap + 1, tap == 8 ? c + 1 : c);
             if (c + 1 < kc) {
@@ -757,7 +754,6 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
     uint32_t a_lds[NA];       // byte offset inside a patch stage
     uint32_t a_keep = 0;      // bit i: slot i is a real patch pixel inside the image (else it must stay zero)
     uint32_t a_slot = 0;      // bit i: slot i exists (pix < 324)
-    int ld_nimg = 0;          // image of the tile whose patch is being loaded (its GroupNorm statistics row)
 #pragma unroll
     for (int i = 0; i < NA; i++) {
         const int pix = (tid + THREADS * i) >> 3;
@@ -768,7 +764,6 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
     auto setupA = [&](const Tile& t) {
         const int y0 = t.tyi * 16 - 1, x0 = t.txi * 16 - 1;   // image coords of patch pixel (0, 0)
         a_keep = 0;
-        ld_nimg = t.nimg;
 #pragma unroll
         for (int i = 0; i < NA; i++) {
             const int pix = (tid + THREADS * i) >> 3;
@@ -790,24 +785,15 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
             a_reg[i] = __builtin_bit_cast(uint4, v);
         }
     };
-    const int cg = mean_rstd ? Cin / G : 1;
+    // GroupNorm: the scale / shift table of the LOADER's image behind the stages (nn_device.h).  The GroupNorm variant keeps
+    // one tile per workgroup (has_next below), so the loader never leaves the first tile's image and the prologue's fill
+    // serves the whole kernel; a GroupNorm variant that walks tiles would refill it where setupA() moves to another image,
+    // behind a barrier that follows the last storeA of the old one.
+    const uint32_t tab_off = (uint32_t)(uintptr_t)(smem + 2 * kAStage + 2 * kBStage);
     auto storeA = [&](int buf, int c) {
-        char* dst = sA + buf * kAStage;
+        const uint32_t dst_off = (uint32_t)(uintptr_t)(sA + buf * kAStage);
         float sc[8], sh[8];
-        if (mean_rstd) {
-            const int ch0 = c * BK + a_chunk * 8;
-            const uint4 gq = *(const uint4*)(gamma + ch0), bq = *(const uint4*)(beta + ch0);
-            const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w}, bw[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int g = (ch0 + k) / cg;
-                const float2 mr = *(const float2*)(mean_rstd + ((size_t)ld_nimg * G + g) * 2);
-                const float gm = bf2f((uint16_t)(gw[k >> 1] >> ((k & 1) * 16)));
-                const float bt = bf2f((uint16_t)(bw[k >> 1] >> ((k & 1) * 16)));
-                sc[k] = gm * mr.y;
-                sh[k] = bt - mr.x * sc[k];
-            }
-        }
+        if (mean_rstd) gn_table_read(tab_off, c * (BK / 8) + a_chunk, sc, sh);
 #pragma unroll
         for (int i = 0; i < NA; i++) {
             if (!((a_slot >> i) & 1u)) continue;
@@ -825,7 +811,11 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
                 }
                 v = make_uint4(w4[0], w4[1], w4[2], w4[3]);
             }
-            *(uint4*)(dst + a_lds[i]) = v;
+            // inline asm: the compiler cannot tell a plain LDS store from the target of the LDS-DMA in flight (the next
+            // weight slice) and would put s_waitcnt vmcnt(0) in front of it; the step's barrier waits for lgkmcnt(0) itself
+            typedef __attribute__((ext_vector_type(4))) uint32_t vec4;
+            const vec4 vv = {v.x, v.y, v.z, v.w};
+            asm volatile("ds_write_b128 %0, %1" ::"v"(dst_off + a_lds[i]), "v"(vv) : "memory");
         }
     };
 
@@ -888,8 +878,10 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
 #pragma unroll
             for (int k = 0; k < 16; k++) acc[a][b][k] = 0.f;
     if (GN) {
+        if (mean_rstd) gn_table_fill(tab_off, tid, THREADS, Cin, G, cur.nimg, mean_rstd, gamma, beta);
         loadA(0);
         issueB(0, 0, 0);
+        if (mean_rstd) gn_table_sync();
         storeA(0, 0);
     } else {
         issueA(0, 0);
@@ -910,7 +902,9 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_patch_stream_kernel(
             if (last_chunk && has_next) setupA(nxt);
             for (int tap = 0; tap < 9; tap++, s++) {
                 const int bufB = s & 1;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                // (GN: the loader's asm LDS stores are not in the compiler's count)
+                if (GN) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 if (!(last_chunk && tap == 8)) {
                     issueB(bufB ^ 1, tap == 8 ? 0 : tap + 1, tap == 8 ? c + 1 : c);
@@ -1352,12 +1346,20 @@ struct TiledArgs {
     int N, H, W, Cin, Cout;
     float* stat_part;
 };
+// A GroupNorm launch (a.mean_rstd) adds the scale / shift table of one image (nn_device.h) behind the kernel's stages: `lds`
+// counts the stages alone, and the reservation, made once per kernel, is the whole CU's LDS because the table grows with Cin.
+constexpr int kCuLds = 160 * 1024;
+static bool gn_table_fits(int lds, int Cin) { return lds + gn_table_bytes(Cin) <= kCuLds; }
 template <auto Kern>
 int launch_tiled(const TiledArgs& a, int lds, int tile_w, int bn, bool persistent)
 {
     const int dev = current_device();
     if (dev < 0) return dev;
-    if (const int r = reserve_lds<Kern>(dev, lds)) return r;
+    if (a.mean_rstd) {
+        if (!gn_table_fits(lds, a.Cin)) return fail(GD_NN_ERR_INVALID_ARG, "GroupNorm scale / shift table of Cin channels does not fit the LDS");
+        lds += gn_table_bytes(a.Cin);
+    }
+    if (const int r = reserve_lds<Kern>(dev, a.mean_rstd ? kCuLds : lds)) return r;
     hipStream_t s = (hipStream_t)a.stream;
     const int tiles_x = (a.W + tile_w - 1) / tile_w, tiles_y = (a.H + 15) / 16, tiles_n = (a.Cout + bn - 1) / bn;
     const int nwg = a.N * tiles_x * tiles_y * tiles_n;
@@ -1625,6 +1627,9 @@ static int launch_patch(void* stream, const void* x, const float* mean_rstd, con
     if (g_force_variant == 2) bn = 256;
     const bool persistent = conv_env().patch_persistent != 0;      // the plain kernel only
     constexpr auto lds = [](int slab) { return 2 * (kPatchPix + 4) * BK * 2 + 2 * slab * BK * 2; };
+    // GroupNorm: the 256-channel slab leaves the table 14336 B (Cin <= 1792); deeper inputs take the 128-channel slab (Cin <=
+    // 5888) -- the same sums in the same order, so the same bits
+    if (mean_rstd && bn == 256 && !gn_table_fits(lds(256), Cin)) bn = 128;
     if (bn == 256)
         return mean_rstd ? launch_tiled<conv3x3_gn_patch_kernel<256, 2, 4, true>>(a, lds(256), 16, 256, false)
                          : launch_tiled<conv3x3_patch_stream_kernel<256, 2, 4, false>>(a, lds(256), 16, 256, persistent);

@@ -20,6 +20,8 @@
 //
 // GN = true: conv(silu(GroupNorm(x))) of diffusers' ResnetBlock2D -- the raw patch chunk goes global -> registers ->
 // x * a[n, c] + b[n, c] -> SiLU -> bf16 -> LDS (a = gamma * rstd, b = beta - mean * a; zero padding after the transform).
+// a, b of the tile's image: computed once per workgroup into a table of 8 * Cin bytes behind the stages (nn_device.h,
+// gn_table_*) and read back per chunk -- 131072 + 8 Cin bytes of LDS in all.
 #pragma once
 #include "nn_device.h"   // (already in at file scope: nn_conv3x3.hip includes it before opening its namespace)
 
@@ -117,22 +119,12 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
                                                                                          (int)(c * (kWideCK * 2)), 0));
         }
     };
-    const int cg = GN ? Cin / G : 1;
     const uint32_t sP_off = (uint32_t)(uintptr_t)sP;
+    // GN: scale / shift of every channel of the tile's image, computed once into the table behind the stages (nn_device.h)
+    const uint32_t tab_off = (uint32_t)(uintptr_t)(smem + kWideLds);
     auto storeP = [&](int buf, int c, int i0, int i1) {
         float sc[8], sh[8];
-        const int ch0 = c * kWideCK + (tid & 3) * 8;
-        const uint4 gq = *(const uint4*)(gamma + ch0), bq = *(const uint4*)(beta + ch0);
-        const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w}, bw[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int g = (ch0 + k) / cg;
-            const float2 mr = *(const float2*)(mean_rstd + ((size_t)nimg * G + g) * 2);
-            const float gm = bf2f((uint16_t)(gw[k >> 1] >> ((k & 1) * 16)));
-            const float bt = bf2f((uint16_t)(bw[k >> 1] >> ((k & 1) * 16)));
-            sc[k] = gm * mr.y;
-            sh[k] = bt - mr.x * sc[k];
-        }
+        gn_table_read(tab_off, c * (kWideCK / 8) + (tid & 3), sc, sh);
 #pragma unroll
         for (int i = i0; i < i1; i++) {
             if (i == 4 && wave == 7) continue;
@@ -184,7 +176,14 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
     const uint32_t a_key = (uint32_t)((fn >> 2) & 3);
 
     const int nsteps = 3 * kc;
-    if (GN) { loadP(0, 0, 3); storeP(0, 0, 0, 3); loadP(0, 3, 5); storeP(0, 0, 3, 5); } else issueP(0, 0);
+    if (GN) {
+        gn_table_fill(tab_off, tid, THREADS, Cin, G, nimg, mean_rstd, gamma, beta);
+        loadP(0, 0, 3);
+        gn_table_sync();
+        storeP(0, 0, 0, 3); loadP(0, 3, 5); storeP(0, 0, 3, 5);
+    } else {
+        issueP(0, 0);
+    }
     issueW(0, 0, 0);
     int s = 0;
     for (int c = 0; c < kc; c++) {

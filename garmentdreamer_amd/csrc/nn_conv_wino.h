@@ -167,22 +167,13 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(
                                                                                     (int)(c * (kWinoCK * 2)), 0));
         }
     };
-    const int cg = GN ? Cin / G : 1;
     const uint32_t sP_off = (uint32_t)(uintptr_t)sP;
+    // GN: scale / shift of every channel of the tile's image, computed once into the table behind P (nn_device.h)
+    const uint32_t tab_off = (uint32_t)(uintptr_t)(smem + kWinoLds);
     auto storeP = [&](int c) {      // GN = true: normalise + SiLU + round, registers -> P
         float sc[8], sh[8];
-        const int ch0 = c * kWinoCK + (tid & 3) * 8;     // (tid + 512 i) & 3 == tid & 3: one channel octet per thread
-        const uint4 gq = *(const uint4*)(gamma + ch0), bq = *(const uint4*)(beta + ch0);
-        const uint32_t gw[4] = {gq.x, gq.y, gq.z, gq.w}, bw[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int g = (ch0 + k) / cg;
-            const float2 mr = *(const float2*)(mean_rstd + ((size_t)nimg * G + g) * 2);
-            const float gm = bf2f((uint16_t)(gw[k >> 1] >> ((k & 1) * 16)));
-            const float bt = bf2f((uint16_t)(bw[k >> 1] >> ((k & 1) * 16)));
-            sc[k] = gm * mr.y;
-            sh[k] = bt - mr.x * sc[k];
-        }
+        // (tid + 512 i) & 3 == tid & 3: one channel octet per thread
+        gn_table_read(tab_off, c * (kWinoCK / 8) + (tid & 3), sc, sh);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             if (i == 2 && wave >= 5) continue;
@@ -264,7 +255,14 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(
 
     const int nsteps = 3 * kc;
     // prologue
-    if (GN) { loadP(0); storeP(0); } else issueP(0);
+    if (GN) {
+        gn_table_fill(tab_off, tid, THREADS, Cin, G, nimg, mean_rstd, gamma, beta);
+        loadP(0);
+        gn_table_sync();
+        storeP(0);
+    } else {
+        issueP(0);
+    }
     issueW(0, 0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

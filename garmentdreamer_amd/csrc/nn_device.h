@@ -73,4 +73,60 @@ __device__ __forceinline__ int swz(int row, int j)
     return (row >> 1) * 256 + (((((row & 1) << 3) | j) ^ ((row >> 1) & 15)) << 4);
 }
 
+// ---- GroupNorm scale / shift table of the convolutions' activation loaders ------------------------------------------
+// A loader that applies GroupNorm on the way to LDS computes x * sc + sh with sc = gamma[c] * rstd[n, g(c)] and
+// sh = beta[c] - mean[n, g(c)] * sc.  Both depend on (image, channel) only, so a workgroup computes them ONCE per image into
+// an LDS table and its K loop reads them back: no global load, no division by the group size and no bf16 conversion per
+// chunk visit.  Layout: per channel octet o = c >> 3 sixteen floats {sc[0..7], sh[0..7]} = 64 contiguous bytes (the
+// loaders own one octet of every pixel they move), 8 * Cin bytes in all.
+constexpr int gn_table_bytes(int Cin) { return 8 * Cin; }
+
+// One channel.  sh is ONE fused multiply-add (what hipcc's contraction made of `bt - mean * sc` before the table existed:
+// the outputs keep their bits).
+__device__ __forceinline__ void gn_scale_shift(float gm, float bt, float mean, float rstd, float& sc, float& sh)
+{
+    sc = gm * rstd;
+    sh = __builtin_fmaf(-mean, sc, bt);
+}
+
+// Threads tid, tid + nthreads, ... each fill one channel of image `nimg` (one division per channel).  The caller puts
+// gn_table_sync() between the fill and the first gn_table_read, and between the last read of an image and a refill.
+// The LDS accesses of the table are inline asm: the compiler cannot tell a plain LDS access from the target of an LDS-DMA
+// in flight and would put s_waitcnt vmcnt(0) in front of it.
+__device__ __forceinline__ void gn_table_fill(uint32_t tab_off, int tid, int nthreads, int Cin, int G, int nimg,
+                                              const float* __restrict__ mean_rstd, const uint16_t* __restrict__ gamma,
+                                              const uint16_t* __restrict__ beta)
+{
+    const int cg = Cin / G;
+    for (int ch = tid; ch < Cin; ch += nthreads) {
+        const float2 mr = *(const float2*)(mean_rstd + ((size_t)nimg * G + ch / cg) * 2);
+        float sc, sh;
+        gn_scale_shift(bf2f(gamma[ch]), bf2f(beta[ch]), mr.x, mr.y, sc, sh);
+        const uint32_t a = tab_off + (uint32_t)(((ch >> 3) * 16 + (ch & 7)) * 4);
+        asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %0, %2 offset:32" ::"v"(a), "v"(sc), "v"(sh) : "memory");
+    }
+}
+
+// The table's own barrier: waits for this wave's LDS operations only, not for global loads or LDS-DMA in flight.
+__device__ __forceinline__ void gn_table_sync()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
+// The sixteen values of one octet: four ds_read_b128 and their wait in ONE statement (the compiler does not count the
+// loads of an asm statement: outputs are early-clobber and complete when the statement ends).
+__device__ __forceinline__ void gn_table_read(uint32_t tab_off, int octet, float (&sc)[8], float (&sh)[8])
+{
+    typedef __attribute__((ext_vector_type(4))) float f32x4;
+    f32x4 a, b, c, d;
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\t"
+                 "ds_read_b128 %3, %4 offset:48\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
+                 : "v"(tab_off + (uint32_t)octet * 64u)
+                 : "memory");
+#pragma unroll
+    for (int k = 0; k < 4; k++) { sc[k] = a[k]; sc[4 + k] = b[k]; sh[k] = c[k]; sh[4 + k] = d[k]; }
+}
+
 }  // namespace gdnn

@@ -182,7 +182,10 @@ size_t gd_nn_conv3x3_wino_weights_bytes(int Cout, int Cin);     /* bytes of u (C
 int gd_nn_conv3x3_wino_weights(void* stream, const void* weight, void* u, int Cout, int Cin);
 int gd_nn_conv3x3_wino_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,
                                const void* residual, void* y, int N, int H, int W, int Cin, int Cout, float* stat_part);
-/* ... with GroupNorm(+SiLU) of the input applied in the loader, as gd_nn_conv3x3_gn_forward(_stats). */
+/* ... with GroupNorm(+SiLU) of the input applied in the loader, as gd_nn_conv3x3_gn_forward(_stats).  The GroupNorm
+ * loaders keep a per-image scale / shift table of 8 * Cin bytes in LDS next to the kernel's stages: this entry takes
+ * Cin <= 384 (GD_NN_ERR_INVALID_ARG beyond), gd_nn_conv3x3_wide_gn_forward Cin <= 4096, gd_nn_conv3x3_gn_forward(_stats)
+ * Cin <= 5888 (the 128-channel slab beyond Cin = 1792). */
 int gd_nn_conv3x3_wino_gn_forward(void* stream, const void* x, const float* mean_rstd, const void* gamma, const void* beta,
                                   int groups, int apply_silu, const void* u, const void* bias, int bias_img_stride,
                                   const void* residual, void* y, int N, int H, int W, int Cin, int Cout, float* stat_part);
