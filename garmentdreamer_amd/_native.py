@@ -135,6 +135,17 @@ MESH_GEOMETRY_SIGNATURES = {
     "gd_mesh_normal_consistency_backward": (_i, [_vp] + [_i] * 2 + [_vp] * 4),     # stream, F P, fn face_nbr dloss dfn
 }
 
+# the second stage's G-buffer losses: enhanced / plain normal map and hole mask, one view per call (include/gd_mesh_losses.h)
+MESH_LOSS_ENHANCED, MESH_LOSS_PLAIN, MESH_LOSS_HOLE = 1, 2, 4
+MESH_LOSS_STATS_WORDS = 6
+MESH_LOSS_SIGNATURES = {
+    "gd_mesh_gbuffer_losses_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "gd_mesh_gbuffer_losses_forward": (_i, [_vp] + [_i] * 3 + [_vp] * 9 + [_f] + [_vp] * 2),   # stream, H W terms, normal position
+                                                    # mask, the same _rf, target normal / mask, camera, epsilon, stats scratch
+    "gd_mesh_gbuffer_losses_backward": (_i, [_vp] + [_i] * 3 + [_vp] * 9 + [_f] + [_vp] * 4),  # ..., epsilon, stats dloss dnormal
+                                                                                               # dposition
+}
+
 # the NeTF stage's texture field: hash-grid encoding and the fused albedo MLP (include/gd_texture.h)
 TEXTURE_MAX_LEVELS = 16
 
@@ -203,7 +214,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
-                + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
+                + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res

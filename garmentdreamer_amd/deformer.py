@@ -1,24 +1,33 @@
-"""One iteration of the mesh deformer's first stage (stage 3 of the reference, ``Garment_Deformer_NeTF/deformation.py``:
-the loop over ``progress_bar_first``): Adam on vertex offsets under a mask loss, the normal-consistency loss and the
-uniform Laplacian loss, on the HIP kernels of ``mesh_deform`` (render) and ``mesh_geometry`` (normals and the two geometry
-losses) -- no CPU path.
+"""Iterations of the mesh deformer (stage 3 of the reference, ``Garment_Deformer_NeTF/deformation.py``).
 
-Out of scope here: the second stage's other losses (``normal``, ``hole_mask``, ``shading`` and its neural shader),
-remeshing, reading the views, the space normalisation and the image dumps.  The second stage's update RULE is built
-(``step(..., only_visible=True)``), so a caller can add its own losses on top of it.
+First stage (the loop over ``progress_bar_first``, ``Deformer.step``): Adam on vertex offsets under a mask loss, the
+normal-consistency loss and the uniform Laplacian loss, on the HIP kernels of ``mesh_deform`` (render) and ``mesh_geometry``
+(normals and the two geometry losses).
+
+Second stage (the loop over ``progress_bar_second``, ``begin_second_stage`` / ``step_second`` / ``adopt_remesh``): the same
+three terms plus the normal-map loss and the hole-mask loss against a frozen copy of the mesh, on the kernels of
+``mesh_losses``, under the visible-rows update ``lr g / (|g| + eps)``.  No CPU path anywhere.
+
+Out of scope here: the second stage's ``shading`` loss and its neural shader (``step_second(extra_loss=...)`` is where a
+caller adds it), remeshing itself (``adopt_remesh`` takes the remeshed mesh), reading the views, the space normalisation
+and the image dumps.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
 from . import mesh_geometry as mg
+from . import mesh_losses as ml
 from ._launch import require_gpu
 from .flat_adam import FlatAdam
 from .mesh_deform import GBufferRenderer
 
 FIRST_STAGE_WEIGHTS = {"mask": 2, "normal_consistency": 0.1, "laplacian": 800}   # deformation.py, loss_weights_first
+# deformation.py, loss_weights_second with the defaults of its arguments; its "shading": 1.0 is left out: the neural shader
+# is not built, a caller adds that term through step_second(extra_loss=...)
+SECOND_STAGE_WEIGHTS = {"hole_mask": 2.0, "mask": 2.0, "normal_consistency": 0.1, "laplacian": 40.0, "normal": 0.8}
 CHANNELS = ["mask", "position", "normal"]
 
 
@@ -79,13 +88,96 @@ class Deformer:
         total = sum(losses[k] * float(w) for k, w in self.weights.items() if w > 0)
         total.backward()
         if only_visible:
-            with torch.no_grad():
-                visible = self.renderer.vertex_visibility(mvps, vertices.detach(), geo.tri, resolutions)
-                g = self.offsets.grad
-                stepped = self.offsets - self.lr * g / (g.abs() + self.eps)
-                self.offsets.copy_(torch.where(visible[:, None], stepped, self.offsets))
+            self._step_visible(mvps, vertices, resolutions)
         else:
             self.optimizer.step()
         out = {k: v.detach() for k, v in losses.items()}
         out["total"] = total.detach()
         return out
+
+    def _step_visible(self, mvps, vertices: torch.Tensor, resolutions) -> None:
+        """The second stage's update (see ``step``): ``lr g / (|g| + eps)`` on the rows visible in these views."""
+        with torch.no_grad():
+            visible = self.renderer.vertex_visibility(mvps, vertices.detach(), self.geometry.tri, resolutions)
+            g = self.offsets.grad
+            stepped = self.offsets - self.lr * g / (g.abs() + self.eps)
+            self.offsets.copy_(torch.where(visible[:, None], stepped, self.offsets))
+
+    # ---- second stage ------------------------------------------------------------------------------------------------
+
+    def begin_second_stage(self, target_normals: Sequence[torch.Tensor], camera_Rs, camera_centers,
+                           weights: Optional[Dict[str, float]] = None, enhanced: bool = True) -> None:
+        """Enter the second stage (deformation.py:264-267).  ``target_normals``: one estimated normal map [H,W,3] in [0,1]
+        per view, in the camera's frame; ``camera_Rs`` [3,3] and ``camera_centers`` [3]: each view's rotation and centre,
+        all on the GPU.  ``weights``: ``SECOND_STAGE_WEIGHTS`` by default; ``enhanced`` selects
+        ``normal_map_loss_enhanced`` (the reference's default) or ``normal_map_loss`` for the ``normal`` term.  The mesh of
+        this moment, ``initial + offsets``, is frozen with its normals as the reference mesh of the hole-mask loss."""
+        n = len(self.mvps)
+        if len(target_normals) != n or len(camera_Rs) != n or len(camera_centers) != n:
+            raise ValueError("Deformer: one normal map, one rotation and one centre per view")
+        self.views = [ml.View(require_gpu("Deformer", "target normal", t, torch.float32, 3), m,
+                              require_gpu("Deformer", "camera R", R, torch.float32),
+                              require_gpu("Deformer", "camera centre", c, torch.float32))
+                      for t, m, R, c in zip(target_normals, self.target_masks, camera_Rs, camera_centers)]
+        self.cameras = [ml.camera_block(view) for view in self.views]
+        self.second_weights = dict(SECOND_STAGE_WEIGHTS if weights is None else weights)
+        self.enhanced = bool(enhanced)
+        with torch.no_grad():
+            self.rf_geometry = self.geometry
+            self.rf_vertices = (self.initial + self.offsets).detach().clone()
+            self.rf_normals = mg.normals(self.rf_vertices, self.rf_geometry)[1]
+
+    def step_second(self, view_indices: Sequence[int],
+                    extra_loss: Optional[Callable[[Sequence[int], Sequence[dict]], torch.Tensor]] = None
+                    ) -> Dict[str, torch.Tensor]:
+        """One second-stage iteration on the views ``view_indices`` (deformation.py:297-355): deform, normals, render the
+        mesh with gradients and the frozen reference mesh without, the five weighted losses (``mask``,
+        ``normal_consistency``, ``laplacian``, ``normal``, ``hole_mask``; the last two from one fused call per view),
+        backward, the visible-rows update of ``step(only_visible=True)``.  ``extra_loss(view_indices, gbuffers)``: a term
+        the caller adds, already weighted -- the seam for the reference's ``shading_loss`` over a shader of the caller's;
+        it is returned as ``extra``.  Returns the detached losses as device tensors; nothing in here waits for the GPU."""
+        if not hasattr(self, "views"):
+            raise RuntimeError("Deformer.step_second: call begin_second_stage first")
+        views = [int(i) for i in view_indices]
+        mvps = [self.mvps[i] for i in views]
+        resolutions = [self.resolutions[i] for i in views]
+        geo, rf = self.geometry, self.rf_geometry
+        self.offsets.grad = None
+        vertices = self.initial + self.offsets
+        face_normals, vertex_normals = mg.normals(vertices, geo)
+        gbuffers = self.renderer.render(mvps, vertices, geo.tri, vertex_normals, resolutions, CHANNELS,
+                                        with_antialiasing=True, topology=geo.topology)
+        with torch.no_grad():
+            gbuffers_rf = self.renderer.render(mvps, self.rf_vertices, rf.tri, self.rf_normals, resolutions, CHANNELS,
+                                               with_antialiasing=True, topology=rf.topology)
+        fused = ml.second_stage_losses([self.views[i] for i in views], gbuffers, gbuffers_rf, self.enhanced,
+                                       cameras=[self.cameras[i] for i in views])
+        losses = {"mask": mg.mask_loss([self.target_masks[i] for i in views], gbuffers),
+                  "normal_consistency": mg.normal_consistency_loss(face_normals, geo),
+                  "laplacian": mg.laplacian_loss(vertices, geo),
+                  "normal": fused["normal"], "hole_mask": fused["hole_mask"]}
+        total = sum(losses[k] * float(w) for k, w in self.second_weights.items() if w > 0)
+        if extra_loss is not None:
+            losses["extra"] = extra_loss(views, gbuffers)
+            total = total + losses["extra"]
+        total.backward()
+        self._step_visible(mvps, vertices, resolutions)
+        out = {k: v.detach() for k, v in losses.items()}
+        out["total"] = total.detach()
+        return out
+
+    def adopt_remesh(self, vertices: torch.Tensor, indices: torch.Tensor) -> None:
+        """Continue the second stage on a remeshed surface (deformation.py:273-295; the remeshing itself is the caller's):
+        ``vertices`` / ``indices`` become the initial mesh with zero offsets, the ``laplacian`` and ``normal_consistency``
+        weights are multiplied by 4 and ``lr`` by 0.25.  The frozen reference mesh keeps its own geometry."""
+        if not hasattr(self, "views"):
+            raise RuntimeError("Deformer.adopt_remesh: call begin_second_stage first")
+        require_gpu("Deformer", "vertices", vertices, torch.float32, 3)
+        require_gpu("Deformer", "indices", indices)
+        self.initial = vertices.detach().clone().contiguous()
+        self.geometry = mg.build_geometry(indices, num_vertices=vertices.shape[0], device=vertices.device)
+        for k in ("laplacian", "normal_consistency"):
+            if k in self.second_weights:
+                self.second_weights[k] *= 4
+        self.offsets = torch.nn.Parameter(torch.zeros_like(self.initial))
+        self.optimizer = FlatAdam([self.offsets], lr=self.lr * 0.25)
