@@ -186,6 +186,36 @@ BAKE_SIGNATURES = {
     "gd_bake_last_error": (C.c_char_p, []),
 }
 
+# the second stage's neural shader and shading loss (include/gd_shader.h, which also fixes the layouts of the buffers);
+# messages go through gd_mesh_last_error
+_u32 = C.c_uint32
+_i64 = C.c_int64
+SHADER_LAYERS = 8
+SHADER_TILE_ROWS = 128
+SHADER_PACKED_ELEMS = 327680
+SHADER_PARAM_ELEMS = 320960
+SHADER_SIGNATURES = {
+    "gd_shader_select_scratch_bytes": (C.c_size_t, [_i64]),
+    "gd_shader_scratch_bytes": (C.c_size_t, [_i64]),
+    "gd_shader_select": (_i, [_vp, _i, _i] + [_vp] * 5 + [_f, _u32, _u32, _i64] + [_vp] * 3),  # stream, H W, normal position
+                                                     # mask view_mask camera, p seed step capacity, index counters scratch
+    "gd_shader_features": (_i, [_vp, _i, _i] + [_vp] * 3 + [_i64] + [_vp] * 3),     # ..., position normal camera, capacity,
+                                                                                     # index counters act
+    "gd_shader_features_points": (_i, [_vp, _i64] + [_vp] * 3 + [_i64] + [_vp] * 2),  # stream, N, position normal view_dir,
+                                                                                     # capacity, counters act
+    "gd_shader_pack": (_i, [_vp] * 4),                                               # stream, params packed packed_t
+    "gd_shader_forward_layer": (_i, [_vp, _i, _i64] + [_vp] * 5),                    # stream, l capacity, counters packed
+                                                                                     # params act logits
+    "gd_shader_backward_input_layer": (_i, [_vp, _i, _i64] + [_vp] * 6),             # ..., counters packed_t act dz dfeat dextra
+    "gd_shader_backward_weight_layer": (_i, [_vp, _i, _i64] + [_vp] * 5),            # ..., counters act dz grad scratch
+    "gd_shader_l1_forward": (_i, [_vp, _i, _i, _i64] + [_vp] * 6),                   # stream, H W capacity, index counters
+                                                                                     # logits rgb loss scratch
+    "gd_shader_l1_backward": (_i, [_vp, _i, _i, _i64] + [_vp] * 7),                  # ..., logits rgb dloss dz dlogits
+    "gd_shader_colour": (_i, [_vp, _i64, _vp, _vp]),                                 # stream, N, logits colour
+    "gd_shader_features_backward": (_i, [_vp, _i, _i] + [_vp] * 2 + [_i64] + [_vp] * 6),  # stream, H W, position camera,
+                                                                    # capacity, index counters dfeat dextra dposition dnormal
+}
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -215,7 +245,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
-                + list(BAKE_SIGNATURES.items()):
+                + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args
@@ -227,6 +257,7 @@ def lib():
 # raster_scene.hip with the scene entries; plan and apply in raster_densify.hip have a channel of their own)
 _ERROR_CHANNELS = (("gd_scene_densify_stats", "gd_scene_last_error"), ("gd_scene_densify_", "gd_scene_densify_last_error"),
                    ("gd_scene_", "gd_scene_last_error"), ("gd_mesh_", "gd_mesh_last_error"),
+                   ("gd_shader_", "gd_mesh_last_error"),
                    ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
                    ("gd_raster_", "gd_raster_last_error"))
 

@@ -6,10 +6,10 @@ normal-consistency loss and the uniform Laplacian loss, on the HIP kernels of ``
 
 Second stage (the loop over ``progress_bar_second``, ``begin_second_stage`` / ``step_second`` / ``adopt_remesh``): the same
 three terms plus the normal-map loss and the hole-mask loss against a frozen copy of the mesh, on the kernels of
-``mesh_losses``, under the visible-rows update ``lr g / (|g| + eps)``.  No CPU path anywhere.
+``mesh_losses``, under the visible-rows update ``lr g / (|g| + eps)``; with a ``neural_shader.NeuralShader`` also the
+``shading`` loss (``mesh_losses.shading_loss``) and the shader's own Adam.  No CPU path anywhere.
 
-Out of scope here: the second stage's ``shading`` loss and its neural shader (``step_second(extra_loss=...)`` is where a
-caller adds it), remeshing itself (``adopt_remesh`` takes the remeshed mesh), reading the views, the space normalisation
+Out of scope here: remeshing itself (``adopt_remesh`` takes the remeshed mesh), reading the views, the space normalisation
 and the image dumps.
 """
 from __future__ import annotations
@@ -25,8 +25,8 @@ from .flat_adam import FlatAdam
 from .mesh_deform import GBufferRenderer
 
 FIRST_STAGE_WEIGHTS = {"mask": 2, "normal_consistency": 0.1, "laplacian": 800}   # deformation.py, loss_weights_first
-# deformation.py, loss_weights_second with the defaults of its arguments; its "shading": 1.0 is left out: the neural shader
-# is not built, a caller adds that term through step_second(extra_loss=...)
+# deformation.py, loss_weights_second with the defaults of its arguments; its "shading": 1.0 is begin_second_stage's
+# shading_weight, applied when a shader is given
 SECOND_STAGE_WEIGHTS = {"hole_mask": 2.0, "mask": 2.0, "normal_consistency": 0.1, "laplacian": 40.0, "normal": 0.8}
 CHANNELS = ["mask", "position", "normal"]
 
@@ -106,19 +106,33 @@ class Deformer:
     # ---- second stage ------------------------------------------------------------------------------------------------
 
     def begin_second_stage(self, target_normals: Sequence[torch.Tensor], camera_Rs, camera_centers,
-                           weights: Optional[Dict[str, float]] = None, enhanced: bool = True) -> None:
+                           weights: Optional[Dict[str, float]] = None, enhanced: bool = True,
+                           target_rgbs: Optional[Sequence[torch.Tensor]] = None, shader=None,
+                           shading_percentage: float = 0.75, shading_weight: float = 1.0, lr_shader: float = 1e-3,
+                           seed: int = 0) -> None:
         """Enter the second stage (deformation.py:264-267).  ``target_normals``: one estimated normal map [H,W,3] in [0,1]
         per view, in the camera's frame; ``camera_Rs`` [3,3] and ``camera_centers`` [3]: each view's rotation and centre,
         all on the GPU.  ``weights``: ``SECOND_STAGE_WEIGHTS`` by default; ``enhanced`` selects
         ``normal_map_loss_enhanced`` (the reference's default) or ``normal_map_loss`` for the ``normal`` term.  The mesh of
-        this moment, ``initial + offsets``, is frozen with its normals as the reference mesh of the hole-mask loss."""
+        this moment, ``initial + offsets``, is frozen with its normals as the reference mesh of the hole-mask loss.
+
+        ``shader``: a ``neural_shader.NeuralShader``; with one, ``target_rgbs`` (one image [H,W,3] per view) is required and
+        ``step_second`` adds ``shading_weight`` x ``shading_loss`` over ``shading_percentage`` of the valid pixels, sampled by
+        ``seed`` and the iteration counter, and steps the shader's Adam (``lr_shader``) next to the vertex update."""
         n = len(self.mvps)
         if len(target_normals) != n or len(camera_Rs) != n or len(camera_centers) != n:
             raise ValueError("Deformer: one normal map, one rotation and one centre per view")
+        if shader is not None and (target_rgbs is None or len(target_rgbs) != n):
+            raise ValueError("Deformer: a shader needs one target image per view")
+        rgbs = [None] * n if shader is None else [require_gpu("Deformer", "target rgb", t, torch.float32, 3) for t in target_rgbs]
         self.views = [ml.View(require_gpu("Deformer", "target normal", t, torch.float32, 3), m,
                               require_gpu("Deformer", "camera R", R, torch.float32),
-                              require_gpu("Deformer", "camera centre", c, torch.float32))
-                      for t, m, R, c in zip(target_normals, self.target_masks, camera_Rs, camera_centers)]
+                              require_gpu("Deformer", "camera centre", c, torch.float32), rgb)
+                      for t, m, R, c, rgb in zip(target_normals, self.target_masks, camera_Rs, camera_centers, rgbs)]
+        self.shader = shader
+        self.shader_optimizer = None if shader is None else shader.optimizer(lr=lr_shader)
+        self.shading_percentage, self.shading_weight = float(shading_percentage), float(shading_weight)
+        self.shading_seed, self.second_iteration = int(seed), 0
         self.cameras = [ml.camera_block(view) for view in self.views]
         self.second_weights = dict(SECOND_STAGE_WEIGHTS if weights is None else weights)
         self.enhanced = bool(enhanced)
@@ -133,9 +147,9 @@ class Deformer:
         """One second-stage iteration on the views ``view_indices`` (deformation.py:297-355): deform, normals, render the
         mesh with gradients and the frozen reference mesh without, the five weighted losses (``mask``,
         ``normal_consistency``, ``laplacian``, ``normal``, ``hole_mask``; the last two from one fused call per view),
-        backward, the visible-rows update of ``step(only_visible=True)``.  ``extra_loss(view_indices, gbuffers)``: a term
-        the caller adds, already weighted -- the seam for the reference's ``shading_loss`` over a shader of the caller's;
-        it is returned as ``extra``.  Returns the detached losses as device tensors; nothing in here waits for the GPU."""
+        with a shader the weighted ``shading`` term, backward, the visible-rows update of ``step(only_visible=True)`` and
+        the shader's Adam step.  ``extra_loss(view_indices, gbuffers)``: a term the caller adds, already weighted; it is
+        returned as ``extra``.  Returns the detached losses as device tensors; nothing in here waits for the GPU."""
         if not hasattr(self, "views"):
             raise RuntimeError("Deformer.step_second: call begin_second_stage first")
         views = [int(i) for i in view_indices]
@@ -157,11 +171,19 @@ class Deformer:
                   "laplacian": mg.laplacian_loss(vertices, geo),
                   "normal": fused["normal"], "hole_mask": fused["hole_mask"]}
         total = sum(losses[k] * float(w) for k, w in self.second_weights.items() if w > 0)
+        if self.shader is not None:
+            self.shader_optimizer.zero_grad()
+            losses["shading"] = ml.shading_loss([self.views[i] for i in views], gbuffers, self.shader,
+                                                self.shading_percentage, self.shading_seed, self.second_iteration)
+            total = total + losses["shading"] * self.shading_weight
+            self.second_iteration += 1
         if extra_loss is not None:
             losses["extra"] = extra_loss(views, gbuffers)
             total = total + losses["extra"]
         total.backward()
         self._step_visible(mvps, vertices, resolutions)
+        if self.shader is not None:
+            self.shader_optimizer.step()
         out = {k: v.detach() for k, v in losses.items()}
         out["total"] = total.detach()
         return out

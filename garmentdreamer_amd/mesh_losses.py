@@ -6,11 +6,15 @@ include/gd_mesh_losses.h) -- no CPU path.
   * ``normal_map_loss(views, gbuffers)``                          <- ``normal_map_loss`` with its default L1
   * ``hole_mask_loss(views, gbuffers, gbuffers_rf)``              <- ``hole_mask_loss`` with its default MSE
   * ``second_stage_losses(views, gbuffers, gbuffers_rf)``         all three from one forward and one backward per view
+  * ``shading_loss(views, gbuffers, shader, shading_percentage)`` <- ``losses/shading.py`` over a ``neural_shader.NeuralShader``
+    (include/gd_shader.h; ``csrc/raster_shader.hip``, ``csrc/raster_shader_mfma.hip``)
 
 A view is a ``View`` of GPU tensors; a G-buffer is the dict ``GBufferRenderer.render`` returns, with ``mask`` [H,W,1],
 ``position`` and ``normal`` [H,W,3].  Each loss is the mean over the views of the per-view term.  Gradients reach
 ``gbuffer["normal"]`` (all three terms) and ``gbuffer["position"]`` (the hole-mask term only: the reference overwrites the
 data of its cosine with the sign, so autograd differentiates the cosine); masks, targets and the ``_rf`` side receive none.
+The shading loss sends gradients to ``position`` (through the encoding and the view direction) and ``normal``, and adds
+those of the shader's parameters into the shader's flat gradient buffer.
 
 The reference states each term as some thirty elementwise ops ending in a boolean-mask gather, which waits for the GPU;
 here a view is two launches forward and one backward, every sum has a fixed order, and nothing synchronises with the host.
@@ -34,6 +38,7 @@ class View(NamedTuple):
     mask: torch.Tensor      # float32 [H,W,1] or [H,W]
     R: torch.Tensor         # float32 [3,3]: the camera's rotation
     center: torch.Tensor    # float32 [3]: the camera's centre, world space
+    rgb: Optional[torch.Tensor] = None    # float32 [H,W,3]: the view's image, read by shading_loss only
 
 
 class _GBufferLosses(torch.autograd.Function):
@@ -150,3 +155,101 @@ def second_stage_losses(views: Sequence[View], gbuffers, gbuffers_rf, enhanced: 
     losses = {"normal_enhanced": out[0], "normal_plain": out[1], "hole_mask": out[2]}
     losses["normal"] = losses["normal_enhanced" if enhanced else "normal_plain"]
     return losses
+
+
+# ---- the shading loss over the neural shader ------------------------------------------------------------------------------
+
+class _Shading(torch.autograd.Function):
+    """The shading loss of one view (0-dim).  ``params`` are the shader's parameters: they make the result require a
+    gradient and receive None, their gradients are ADDED into the shader's flat gradient buffer by the kernels."""
+
+    @staticmethod
+    def forward(ctx, position, normal, mask, view_mask, rgb, camera, shader, p, seed, step, capacity, record, *params):
+        from . import neural_shader as ns
+        dev = position.device
+        H, W = position.shape[0], position.shape[1]
+        cap = C.c_int64(capacity)
+        rows = ns.rows_of(capacity)
+        index = torch.empty(capacity, dtype=torch.int32, device=dev)
+        counters = torch.empty(4, dtype=torch.int32, device=dev)
+        act = torch.empty(rows * ns.ACT_WIDTH, dtype=torch.bfloat16, device=dev)
+        logits = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        work = ns.workspace(capacity, dev)
+        launch("gd_shader_select", dev, H, W, normal, position, mask, view_mask, camera, C.c_float(p), C.c_uint32(seed),
+               C.c_uint32(step), cap, index, counters, scratch(_native.lib().gd_shader_select_scratch_bytes(H * W), dev))
+        launch("gd_shader_features", dev, H, W, position, normal, camera, cap, index, counters, act)
+        shader.forward_layers(capacity, counters, act, logits)
+        launch("gd_shader_l1_forward", dev, H, W, cap, index, counters, logits, rgb, loss, work)
+        ctx.save_for_backward(position, camera, index, counters, act, logits, rgb)
+        ctx.shader, ctx.capacity, ctx.work = shader, capacity, work
+        record.update(index=index, counters=counters, logits=logits)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import neural_shader as ns
+        position, camera, index, counters, act, logits, rgb = ctx.saved_tensors
+        shader, capacity = ctx.shader, ctx.capacity
+        dev = position.device
+        H, W = position.shape[0], position.shape[1]
+        cap = C.c_int64(capacity)
+        rows = ns.rows_of(capacity)
+        dz = torch.empty(rows * ns.DZ_WIDTH, dtype=torch.bfloat16, device=dev)
+        dfeat = torch.empty(rows, 32, dtype=torch.float32, device=dev)
+        dextra = torch.empty(rows, 32, dtype=torch.float32, device=dev)
+        launch("gd_shader_l1_backward", dev, H, W, cap, index, counters, logits, rgb,
+               dloss.reshape(1).to(torch.float32).contiguous(), dz, None)
+        for l in range(ns.LAYERS - 1, -1, -1):
+            launch("gd_shader_backward_weight_layer", dev, l, cap, counters, act, dz, shader.flat_grad, ctx.work)
+            launch("gd_shader_backward_input_layer", dev, l, cap, counters, shader.packed_t, act, dz, dfeat, dextra)
+        dposition, dnormal = torch.empty_like(position), torch.empty_like(position)
+        launch("gd_shader_features_backward", dev, H, W, position, camera, cap, index, counters, dfeat, dextra, dposition,
+               dnormal)
+        return (dposition, dnormal) + (None,) * (10 + len(ctx.shader.parameters()))
+
+
+def shading_loss(views: Sequence[View], gbuffers, shader, shading_percentage: float = 1.0, seed: int = 0, step: int = 0,
+                 capacity: Optional[int] = None) -> torch.Tensor:
+    """Mean over the views of the L1 distance between ``shader(position, normal, view_dir)`` and ``view.rgb`` over a sample
+    of the pixels that both masks cover and that face the camera (include/gd_shader.h).  0-dim.  A valid pixel is kept when
+    ``hash32(seed, step, pixel) < shading_percentage 2^32``: the number kept is binomial around ``shading_percentage`` of the
+    valid pixels, where the reference keeps exactly ``int(n p)`` drawn by the host's ``randperm`` -- a stated deviation, paid
+    for by not waiting for the GPU.  At most ``capacity`` pixels (``H W`` by default) are shaded, the first in pixel order;
+    the rest is counted.  Gradients reach ``gbuffer["position"]`` and ``gbuffer["normal"]``; those of the shader's parameters
+    are ADDED into ``shader.flat_grad``.  A view that keeps nothing adds 0 (the reference: NaN).
+
+    After a call ``shading_loss.count`` and ``shading_loss.dropped`` hold int32 [views] device tensors, and
+    ``shading_loss.last`` per view the index list, the counters and the logits of the shaded points."""
+    from .neural_shader import NeuralShader, check_capacity
+    name = "shading_loss"
+    if not isinstance(shader, NeuralShader):
+        raise TypeError(f"{name}: shader must be a neural_shader.NeuralShader")
+    if len(views) == 0 or len(views) != len(gbuffers):
+        raise ValueError(f"{name}: one G-buffer per view, and at least one view")
+    p = float(shading_percentage)
+    if not p >= 0.0:
+        raise ValueError(f"{name}: shading_percentage must not be negative")
+    if not (0 <= int(seed) < 1 << 32 and 0 <= int(step) < 1 << 32):
+        raise ValueError(f"{name}: seed and step must fit 32 bits")
+    params = shader.parameters()
+    total, records = None, []
+    for view, gbuffer in zip(views, gbuffers):
+        if view.rgb is None:
+            raise ValueError(f"{name}: the view has no rgb image (View(normal, mask, R, center, rgb))")
+        if not isinstance(view.rgb, torch.Tensor) or view.rgb.dim() != 3 or view.rgb.shape[-1] != 3:
+            raise ValueError(f"{name}: view.rgb must be [H,W,3]")
+        normal, position, mask = _gbuffer(name, "gbuffer", gbuffer)
+        rgb = _image(name, "view.rgb", view.rgb, 3, normal).detach()
+        view_mask = _image(name, "view.mask", view.mask, 1, normal).detach()
+        H, W = normal.shape[0], normal.shape[1]
+        cap = check_capacity(name, H * W if capacity is None else capacity)
+        record = {}
+        one = _Shading.apply(position, normal, mask.detach(), view_mask, rgb, camera_block(view).detach(), shader, p,
+                             int(seed), int(step), cap, record, *params)
+        records.append(record)
+        total = one if total is None else total + one
+    shading_loss.last = records
+    counters = torch.stack([r["counters"] for r in records])
+    shading_loss.count, shading_loss.dropped = counters[:, 0], counters[:, 1]
+    return total / len(views)
