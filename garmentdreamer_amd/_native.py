@@ -216,6 +216,18 @@ SHADER_SIGNATURES = {
                                                                     # capacity, index counters dfeat dextra dposition dnormal
 }
 
+# the loss head of the NeTF stage's texture fit (include/gd_fit.h); messages go through gd_mesh_last_error
+FIT_PIXELS_PER_LANE = 4
+FIT_PIXELS_PER_PARTIAL = 256
+FIT_FINAL_THREADS = 256
+FIT_STATS_WORDS = 4
+FIT_SIGNATURES = {
+    "gd_fit_loss_scratch_bytes": (C.c_size_t, [_i64]),
+    "gd_fit_loss_forward": (_i, [_vp] + [_i] * 3 + [_vp] * 13),                      # stream, H W flip_rows, c_aa a_aa p_aa n_aa
+                                                                 # center rgb tmask bg, image cosinesview m stats scratch
+    "gd_fit_loss_backward": (_i, [_vp] + [_i] * 3 + [_vp] * 8),                      # ..., c_aa a_aa rgb bg m stats dloss dc_aa
+}
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -245,7 +257,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
-                + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()):
+                + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args
@@ -257,7 +269,7 @@ def lib():
 # raster_scene.hip with the scene entries; plan and apply in raster_densify.hip have a channel of their own)
 _ERROR_CHANNELS = (("gd_scene_densify_stats", "gd_scene_last_error"), ("gd_scene_densify_", "gd_scene_densify_last_error"),
                    ("gd_scene_", "gd_scene_last_error"), ("gd_mesh_", "gd_mesh_last_error"),
-                   ("gd_shader_", "gd_mesh_last_error"),
+                   ("gd_shader_", "gd_mesh_last_error"), ("gd_fit_", "gd_mesh_last_error"),
                    ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
                    ("gd_raster_", "gd_raster_last_error"))
 

@@ -10,7 +10,8 @@ netf/render/texture_encoder.py:8-37 (tiny-cuda-nn's "Grid"/"Hash", linear interp
   * ``NeTFRenderer``          ``MeshRenderer`` that evaluates a field on every pixel with the coverage as ``mask``: no
                               ``mask.any()``, no boolean indexing, nothing that waits for the GPU
                               ``export_mesh`` bakes the field into a UV atlas and writes the textured OBJ
-                              (``texture_bake.py``)
+                              (``texture_bake.py``); ``fit_texture_from_mesh`` fits the field to captured views
+                              (``texture_fit.py``)
 
 Gradients follow ``.grad`` semantics at the C level (every kernel ADDS into the buffer it is given).  A parameter that
 ``TextureFieldOptimizer`` has re-seated carries ``_gd_grad_sink`` (a view of the optimizer's flat gradient buffer, as
@@ -405,6 +406,14 @@ class NeTFRenderer(MeshRenderer):
 
     def _texture(self, xyzs, mask):
         return self.texture_fn(xyzs, mask).float()
+
+    def fit_texture_from_mesh(self, views, iters=600, resolution=1024, hashgrid_lr=0.01, mlp_lr=0.001, seed=0,
+                              save_path=None, optimizer=None):
+        """``Renderer.fit_texture_from_mesh`` (mesh_renderer.py:158-240): ``iters`` Adam steps on the masked MSE between the
+        render and one of ``views`` (``texture_fit.FitView``) per step; returns the loss history as one device tensor
+        [iters].  See ``texture_fit.fit_texture``."""
+        from . import texture_fit
+        return texture_fit.fit_texture(self, views, iters, resolution, hashgrid_lr, mlp_lr, seed, save_path, optimizer)
 
     def export_mesh(self, save_path, texture_resolution=2048, padding=16, reverse=False, vt=None, ft=None):
         """``Renderer.export_mesh`` (mesh_renderer.py:260-313) plus optional UVs: bakes ``texture_fn`` into the atlas ``vt`` /
