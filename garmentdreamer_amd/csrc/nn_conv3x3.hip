@@ -396,6 +396,145 @@ __device__ __forceinline__ void patch_col(int fn, int& rr, int& fx)
 constexpr int kTrRow = 80;                 // bytes per pixel row of the epilogue's transposition buffer (64 + pad)
 constexpr int kTrWave = 64 * kTrRow;       // per wave: 64 pixels x 32 channels
 
+// ---- residual tile by LDS-DMA (conv3x3_gn_patch_kernel here, nn_conv_wide.h, nn_conv_wino.h) --------------------------------
+// Read in the MFMA result layout, the residual is 8 bytes per lane with consecutive lanes on consecutive PIXELS: one load
+// instruction touches 64 cache lines, the loads stand in the epilogue where nothing covers them, and each is followed by
+// s_waitcnt vmcnt(0) (the plain LDS store behind it cannot be told from an LDS-DMA target): sixteen round trips in a row per
+// 32-channel block.  Instead a wave
+// fetches its share of one epilogue round -- the 64 pixels x 32 channels of one pass of the transposition buffer -- with
+// four LDS-DMA instructions of 16 pixels x 64 contiguous bytes, ahead of the round that adds it, and the round reads the
+// values back from LDS in its own (pixel, channel quad) pattern.  The arithmetic (acc + bias, + residual, one rounding)
+// and its order are those of the per-lane loads.
+// LDS image of a round (kResRound bytes per wave): pixel P = j * 32 + fn (row pair j, MFMA column fn) at P * 64, its
+// 16-byte chunk c at slot c ^ ((P >> 2) & 3).  LDS-DMA writes lane-linearly, so the swizzle is applied to WHICH chunk a lane
+// fetches.  A ds_read_b64 of the round (32 lanes = 32 pixels, one channel quad) then touches every 8-byte bank pair of its
+// half (fk) exactly twice: two-way, 4 cycles per read more than a conflict-free one, on eight reads per round.
+constexpr int kResRound = 64 * 64;
+
+// Byte offsets of the piece `lane` fetches in the even (pixels fn 0..15) and odd (fn 16..31) DMA instructions of a row
+// pair, relative to pixel (row 0, column 0) of the wave's 2 x 16-pixel block; pix_bytes = Cout * 2, img_row_bytes = W * Cout * 2
+__device__ __forceinline__ void res_tile_lane(int lane, uint32_t pix_bytes, uint32_t img_row_bytes, uint32_t (&off)[2])
+{
+    const uint32_t chunk = (uint32_t)((lane & 3) ^ ((lane >> 4) & 3));
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        int rr, fx;
+        patch_col(16 * h + (lane >> 2), rr, fx);
+        off[h] = (uint32_t)rr * img_row_bytes + (uint32_t)fx * pix_bytes + chunk * 16u;
+    }
+}
+
+// One round of one wave: `base` = byte offset of (first pixel of the wave's block, first channel of the round) in the
+// residual tensor (wave-uniform), two_rows = 2 * img_row_bytes (the second row pair), slot = the wave's kResRound bytes
+__device__ __forceinline__ void res_tile_issue(__amdgpu_buffer_rsrc_t rs, const uint32_t (&off)[2], uint32_t base,
+                                               uint32_t two_rows, char* slot)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) bload_lds16(rs, off[i & 1], base + (uint32_t)(i >> 1) * two_rows, slot + i * 1024);
+}
+
+typedef __attribute__((ext_vector_type(2))) uint32_t res_u32x2;
+typedef __attribute__((ext_vector_type(4))) uint32_t res_u32x4;
+
+// The lane's eight values of the round: r[j][q] = channels 8 q + 4 fk .. + 3 of pixel j * 32 + fn.  Inline asm, reads and
+// their wait in one statement: the compiler cannot tell a plain LDS read from the target of an LDS-DMA in flight (the
+// next round's) and would put s_waitcnt vmcnt(0) in front of it.
+__device__ __forceinline__ void res_tile_read(uint32_t slot_off, int lane, res_u32x2 (&r)[2][4])
+{
+    const int fn = lane & 31, fk = lane >> 5;
+    const uint32_t a0 = slot_off + (uint32_t)(fn * 64 + 8 * fk), key = (uint32_t)((fn >> 2) & 3);
+    const uint32_t q0 = a0 + (key << 4), q1 = a0 + ((1u ^ key) << 4), q2 = a0 + ((2u ^ key) << 4), q3 = a0 + ((3u ^ key) << 4);
+    asm volatile("ds_read_b64 %0, %8\n\tds_read_b64 %1, %9\n\tds_read_b64 %2, %10\n\tds_read_b64 %3, %11\n\t"
+                 "ds_read_b64 %4, %8 offset:2048\n\tds_read_b64 %5, %9 offset:2048\n\t"
+                 "ds_read_b64 %6, %10 offset:2048\n\tds_read_b64 %7, %11 offset:2048\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[0][2]), "=&v"(r[0][3]), "=&v"(r[1][0]), "=&v"(r[1][1]),
+                   "=&v"(r[1][2]), "=&v"(r[1][3])
+                 : "v"(q0), "v"(q1), "v"(q2), "v"(q3)
+                 : "memory");
+}
+
+// What a wave needs to know of its tile for the rounds below (FULL tiles only: no pixel or channel is masked)
+struct ResTile {
+    uint16_t* out;
+    size_t pix0;            // index of the first pixel of the wave's block in the N x H x W image stack
+    int Cout;
+    float* stat_img;        // stat_part + nimg * (Cout / 4) * stat_rows * 2, or NULL
+    int stat_rows, stat_row;   // rows per (image, channel quad); this wave's first row of the 16 x 16-pixel tile it lies in
+    bool stat_ok;           // (wide tile: its 16-column half exists in the 16 x 16 grid)
+};
+
+// One round of the epilogue with the residual from LDS: the wave's 64 pixels (row pairs acc0, acc1) x 32 channels from
+// co0.  v = acc + bias; v += residual; one rounding; through the transposition buffer `tr_off` (kTrWave bytes, wave-private)
+// to 64 contiguous bytes per pixel and store instruction; optional GroupNorm partial sums of the stored values -- the
+// arithmetic of patch_epilogue below, value by value.  bb: the lane's four bias quads of the round (zeros without bias),
+// loaded by the caller BEFORE the DMAs in flight (vmcnt retires in order).  The caller has waited for the round's DMA;
+// after_read() runs once the slot has been read (the caller re-uses it); pix_of(pr) is the offset, in pixels from pix0,
+// of pixel pr = j * 32 + fn of the wave's block (PatchPix for the kernels that order their columns by patch_col).  Every LDS
+// access here is inline asm, see res_tile_read.
+struct PatchPix {
+    int W;
+    __device__ __forceinline__ int operator()(int pr) const
+    {
+        int rr, fx;
+        patch_col(pr & 31, rr, fx);
+        return (2 * (pr >> 5) + rr) * W + fx;
+    }
+};
+
+template <class PixOf, class AfterRead>
+__device__ __forceinline__ void res_round(const f32x16& acc0, const f32x16& acc1, const uint2 (&bb)[4], uint32_t slot_off,
+                                          uint32_t tr_off, int lane, const ResTile& t, int co0, PixOf pix_of,
+                                          AfterRead after_read)
+{
+    const int fk = lane >> 5, fn = lane & 31;
+    res_u32x2 rv[2][4];
+    res_tile_read(slot_off, lane, rv);
+    after_read();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int co = co0 + 8 * q + 4 * fk;
+        const float bv[4] = {bf2f((uint16_t)(bb[q].x & 0xffff)), bf2f((uint16_t)(bb[q].x >> 16)),
+                             bf2f((uint16_t)(bb[q].y & 0xffff)), bf2f((uint16_t)(bb[q].y >> 16))};
+        float2 st = make_float2(0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) v[e] = (j ? acc1 : acc0)[4 * q + e] + bv[e];
+            const uint32_t r0 = rv[j][q][0], r1 = rv[j][q][1];
+            v[0] += bf2f((uint16_t)(r0 & 0xffff)); v[1] += bf2f((uint16_t)(r0 >> 16));
+            v[2] += bf2f((uint16_t)(r1 & 0xffff)); v[3] += bf2f((uint16_t)(r1 >> 16));
+            uint2 o;
+            o.x = pack_bf16(v[0], v[1]);
+            o.y = pack_bf16(v[2], v[3]);
+            const res_u32x2 ov = {o.x, o.y};
+            asm volatile("ds_write_b64 %0, %1" ::"v"(tr_off + (uint32_t)((j * 32 + fn) * kTrRow + 16 * q + 8 * fk)), "v"(ov)
+                         : "memory");
+            if (t.stat_img) stat_accumulate(st, o);
+        }
+        if (t.stat_img) {
+            const float sx = row16_sum(st.x), sy = row16_sum(st.y);
+            if ((lane & 15) == 0 && t.stat_ok)
+                *(float2*)(t.stat_img + ((size_t)(co >> 2) * t.stat_rows + t.stat_row + ((lane >> 4) & 1)) * 2) =
+                    make_float2(sx, sy);
+        }
+    }
+    // LDS operations of one wave execute in order: the reads see the writes above
+    res_u32x4 tv[4];
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1280\n\tds_read_b128 %2, %4 offset:2560\n\t"
+                 "ds_read_b128 %3, %4 offset:3840\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(tv[0]), "=&v"(tv[1]), "=&v"(tv[2]), "=&v"(tv[3])
+                 : "v"(tr_off + (uint32_t)((lane >> 2) * kTrRow + (lane & 3) * 16))
+                 : "memory");
+    static_assert(16 * kTrRow == 1280, "offsets of the four reads");
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int pr = (lane >> 2) + 16 * i;      // pixel of the wave's block; the lane's 8-channel chunk is lane & 3
+        *(uint4*)(t.out + (t.pix0 + (size_t)pix_of(pr)) * t.Cout + co0 + 8 * (lane & 3)) =
+            make_uint4(tv[i][0], tv[i][1], tv[i][2], tv[i][3]);
+    }
+}
+
 // Epilogue of the patch-staged kernels: out = bf16(acc + bias (+ residual)), optional GroupNorm partial sums.
 // In the MFMA result layout a lane owns 4 consecutive channels of a pixel and neighbouring lanes are neighbouring
 // PIXELS, so a direct store instruction is 64 separate 8-byte writes (one per cache line): with those the stores cost
@@ -486,7 +625,8 @@ __device__ __forceinline__ void patch_epilogue(f32x16 (&acc)[FA][FB], char* tr, 
 // GN = true: GroupNorm(+SiLU) applied in the loader (register staged).  GN = false: plain convolution, the patch
 // is fetched by LDS-DMA like the weights -- 41 LDS-DMA wave-instructions per 64 input channels (5.2 patch + 36
 // weight pieces) instead of the implicit-GEMM kernel's 72.
-template <int BN, int WN, int WM, bool GN>
+// RES: the launch has a residual and may fetch it by LDS-DMA (below); launches without one run RES = false.
+template <int BN, int WN, int WM, bool GN, bool RES>
 __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
     const uint16_t* __restrict__ in, const uint16_t* __restrict__ wt, const uint16_t* __restrict__ bias,
     int bias_img_stride, const uint16_t* __restrict__ residual, uint16_t* __restrict__ out, int Nimg, int H, int W,
@@ -636,6 +776,32 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
             bload_lds16(rs_in, a_goff[i], (uint32_t)c * (BK * 2), dst + (wave * 64 + THREADS * i) * 16);
         }
     };
+    // ---- residual tile by LDS-DMA (res_tile_* above): a round = one 32-channel block a of the epilogue, 4 KB per wave, FA
+    // rounds.  Taken by FULL tiles only (every pixel inside the image, the whole channel slab below Cout) of a residual tensor
+    // below 4 GiB (32-bit buffer range); every other tile keeps the per-lane loads of patch_epilogue.
+    //   round 0: issued in the last chunk's first step into the patch stage that is idle then (with kc = 1 that is the first
+    //            step), landed under the step's MFMAs: awaited by the next step's vmcnt(0);
+    //   rounds 1, 2: issued after the barrier that ends the K loop, into the two filter stages (32 KB each with BN = 256;
+    //            BN = 128 has two rounds, and both its filter stages hold round 1);
+    //   round 3: into round 0's slot once round 0 has read it.
+    // The transposition buffer stays where it is, in the last chunk's patch stage.
+    static_assert(FA == 2 || FA == 4, "rounds of the residual tile");
+    const bool dma = RES && residual != nullptr && (Cout & 7) == 0 && tyi * 16 + 16 <= H && txi * 16 + 16 <= W && n0 + BN <= Cout &&
+                     (uint64_t)Nimg * (uint64_t)(H * W) * (uint64_t)Cout * 2u < (1ull << 32);
+    const uint32_t res_pix = (uint32_t)Cout * 2u, res_row = (uint32_t)W * res_pix;
+    const __amdgpu_buffer_rsrc_t rs_res = buffer_rsrc(residual, (uint32_t)Nimg * (uint32_t)(H * W) * res_pix);
+    auto res_slot = [&](int r) -> char* {
+        if (r == 0 || r == 3) return sA + (kc & 1) * kAStage + wave * kResRound;
+        return sB + (r - 1) * (8 * kResRound) + wave * kResRound;
+    };
+    auto issueR = [&](int r) {
+        uint32_t off[2];
+        res_tile_lane(lane, res_pix, res_row, off);
+        const uint32_t base = (uint32_t)((nimg * H + tyi * 16 + 4 * wp) * W + txi * 16) * res_pix +
+                              (uint32_t)(n0 + wc * (BN / WN) + r * 32) * 2u;
+        res_tile_issue(rs_res, off, base, 2u * res_row, res_slot(r));
+    };
+
     if (GN) {
         if (mean_rstd) gn_table_fill(tab_off, tid, THREADS, Cin, G, nimg, mean_rstd, gamma, beta);
         loadA(0);
@@ -663,6 +829,8 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
                 } else if (tap == 0) {
                     issueA((c + 1) & 1, c + 1);   // the other patch stage was last read in chunk c - 1
                 }
+            } else if (tap == 0 && dma) {
+                issueR(0);      // every wave has left chunk kc - 2: its stage is free
             }
             const char* pb = sB + bufB * kBStage;
             const int tapoff = (tap / 3) * kPatch + (tap % 3);
@@ -693,6 +861,38 @@ __global__ __launch_bounds__(64 * WN * WM) void conv3x3_gn_patch_kernel(
     // ---- epilogue: every wave is done with the patch stage of the last chunk once all have passed this barrier; its
     // memory becomes the transposition buffer
     if (GD_PATCH_EPI != 2) __syncthreads();
+    if (GD_PATCH_EPI == 0 && dma) {
+        // Bias of the lane's channel quads FIRST: vmcnt retires in order, a bias load behind a residual DMA would wait for
+        // it.  The waits on the DMAs are counted by hand: a round waits until only the DMAs issued after its own may be
+        // outstanding (stores issued in between only make the wait stricter).
+        const uint32_t tr_off = (uint32_t)(uintptr_t)(sA + ((kc - 1) & 1) * kAStage + wave * kTrWave);
+        const uint16_t* bias_d = bias ? bias + (size_t)nimg * bias_img_stride : nullptr;
+        uint2 bb[FA][4];
+#pragma unroll
+        for (int a = 0; a < FA; a++)
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                bb[a][q] = bias_d ? *(const uint2*)(bias_d + n0 + wc * (BN / WN) + a * 32 + 8 * q + 4 * fk) : make_uint2(0u, 0u);
+        asm volatile("" ::: "memory");
+        issueR(1);
+        if (FA == 4) issueR(2);
+        ResTile t;
+        t.out = out; t.Cout = Cout;
+        t.pix0 = ((size_t)nimg * H + (tyi * 16 + 4 * wp)) * W + txi * 16;
+        t.stat_rows = tpi * 8;
+        t.stat_img = stat_part ? stat_part + (size_t)nimg * (Cout >> 2) * t.stat_rows * 2 : nullptr;
+        t.stat_row = (tyi * tiles_x + txi) * 8 + wp * 2;
+        t.stat_ok = true;
+#pragma unroll
+        for (int r = 0; r < FA; r++) {
+            if (r == FA - 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");        // two later rounds may be in flight
+            else if (r == FA - 2 && r > 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // one
+            else if (r == FA - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            res_round(acc[r][0], acc[r][1], bb[r], (uint32_t)(uintptr_t)res_slot(r), tr_off, lane, t,
+                      n0 + wc * (BN / WN) + r * 32, PatchPix{W}, [&] { if (FA == 4 && r == 0) issueR(3); });   // slot 0 has been read
+        }
+        return;
+    }
     patch_epilogue<BN, WN, FA, FB>(acc, sA + ((kc - 1) & 1) * kAStage + wave * kTrWave, nimg, tyi, txi, n0, wc, wp, lane, H, W,
                                    Cout, bias, bias_img_stride, residual, out, stat_part, tpi, tiles_x);
 }
@@ -1630,11 +1830,15 @@ static int launch_patch(void* stream, const void* x, const float* mean_rstd, con
     // GroupNorm: the 256-channel slab leaves the table 14336 B (Cin <= 1792); deeper inputs take the 128-channel slab (Cin <=
     // 5888) -- the same sums in the same order, so the same bits
     if (mean_rstd && bn == 256 && !gn_table_fits(lds(256), Cin)) bn = 128;
-    if (bn == 256)
-        return mean_rstd ? launch_tiled<conv3x3_gn_patch_kernel<256, 2, 4, true>>(a, lds(256), 16, 256, false)
-                         : launch_tiled<conv3x3_patch_stream_kernel<256, 2, 4, false>>(a, lds(256), 16, 256, persistent);
-    return mean_rstd ? launch_tiled<conv3x3_gn_patch_kernel<128, 2, 4, true>>(a, lds(128), 16, 128, false)
-                     : launch_tiled<conv3x3_patch_stream_kernel<128, 2, 4, false>>(a, lds(128), 16, 128, persistent);
+    // (a launch with a residual runs the instantiation that may fetch it by LDS-DMA, every other launch the one without)
+    if (bn == 256) {
+        if (!mean_rstd) return launch_tiled<conv3x3_patch_stream_kernel<256, 2, 4, false>>(a, lds(256), 16, 256, persistent);
+        return residual ? launch_tiled<conv3x3_gn_patch_kernel<256, 2, 4, true, true>>(a, lds(256), 16, 256, false)
+                        : launch_tiled<conv3x3_gn_patch_kernel<256, 2, 4, true, false>>(a, lds(256), 16, 256, false);
+    }
+    if (!mean_rstd) return launch_tiled<conv3x3_patch_stream_kernel<128, 2, 4, false>>(a, lds(128), 16, 128, persistent);
+    return residual ? launch_tiled<conv3x3_gn_patch_kernel<128, 2, 4, true, true>>(a, lds(128), 16, 128, false)
+                    : launch_tiled<conv3x3_gn_patch_kernel<128, 2, 4, true, false>>(a, lds(128), 16, 128, false);
 }
 
 
@@ -1768,8 +1972,11 @@ static int launch_wino(void* stream, const void* x, const float* mean_rstd, cons
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_wino: GroupNorm needs gamma, beta and Cin % groups == 0");
     const TiledArgs a = {stream, x, mean_rstd, gamma, beta, groups, apply_silu, u, bias, bias_img_stride, residual, y,
                          N, H, W, Cin, Cout, stat_part};
-    return mean_rstd ? launch_tiled<conv3x3_wino_kernel<true>>(a, kWinoLds, 16, 128, false)
-                     : launch_tiled<conv3x3_wino_kernel<false>>(a, kWinoLds, 16, 128, false);
+    if (residual)
+        return mean_rstd ? launch_tiled<conv3x3_wino_kernel<true, true>>(a, kWinoLds, 16, 128, false)
+                         : launch_tiled<conv3x3_wino_kernel<false, true>>(a, kWinoLds, 16, 128, false);
+    return mean_rstd ? launch_tiled<conv3x3_wino_kernel<true, false>>(a, kWinoLds, 16, 128, false)
+                     : launch_tiled<conv3x3_wino_kernel<false, false>>(a, kWinoLds, 16, 128, false);
 }
 
 int gd_nn_conv3x3_wino_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,
@@ -1828,8 +2035,11 @@ static int launch_wide(void* stream, const void* x, const float* mean_rstd, cons
         return fail(GD_NN_ERR_INVALID_ARG, "conv3x3_wide: GroupNorm needs gamma, beta and Cin % groups == 0");
     const TiledArgs a = {stream, x, mean_rstd, gamma, beta, groups, apply_silu, u, bias, bias_img_stride, residual, y,
                          N, H, W, Cin, Cout, stat_part};
-    return mean_rstd ? launch_tiled<conv3x3_wide_kernel<true>>(a, kWideLds, 32, 128, false)
-                     : launch_tiled<conv3x3_wide_kernel<false>>(a, kWideLds, 32, 128, false);
+    if (residual)      // + the LDS of two rounds of the residual tile
+        return mean_rstd ? launch_tiled<conv3x3_wide_kernel<true, true>>(a, kWideLds, 32, 128, false)
+                         : launch_tiled<conv3x3_wide_kernel<false, true>>(a, kWideLds, 32, 128, false);
+    return mean_rstd ? launch_tiled<conv3x3_wide_kernel<true, false>>(a, kWideStages, 32, 128, false)
+                     : launch_tiled<conv3x3_wide_kernel<false, false>>(a, kWideStages, 32, 128, false);
 }
 
 int gd_nn_conv3x3_wide_forward(void* stream, const void* x, const void* u, const void* bias, int bias_img_stride,

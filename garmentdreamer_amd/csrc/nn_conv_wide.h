@@ -13,7 +13,8 @@
 //     LDS-DMA instruction moves 1 KB of consecutive memory) + a third of the 39 KB patch chunk: 0.77 KB of LDS-DMA per
 //     MFMA and wave against 1.3 KB (128 x 256 direct tile) and 2.4 KB (Winograd form, nn_conv_wino.h);
 //   * fragment reads 6 per 8 MFMAs (filter fragment reused by 4 pixel blocks, pixel fragment by 2 channel blocks).
-// LDS: 2 patch stages [18 x 34 px][32 ch] (40 KB each incl. padding) + 2 filter stages (24 KB) = 128 KB.
+// LDS: 2 patch stages [18 x 34 px][32 ch] (40 KB each incl. padding) + 2 filter stages (24 KB) = 128 KB, + 16 KB for the
+// epilogue's residual tile = 144 KB in a launch with a residual (RES).
 // 64-byte rows: 16-byte chunk c of patch pixel p at chunk c ^ ((p >> 2) & 3), of filter row r at c ^ ((r >> 2) & 3) -- the
 // sixteen lanes of a ds_read_b128 service group read sixteen CONSECUTIVE pixels of a patch row (patch_col), whose
 // (p & 3, (p >> 2) & 3) pairs are all different whatever the tap shift: conflict free.
@@ -21,7 +22,8 @@
 // GN = true: conv(silu(GroupNorm(x))) of diffusers' ResnetBlock2D -- the raw patch chunk goes global -> registers ->
 // x * a[n, c] + b[n, c] -> SiLU -> bf16 -> LDS (a = gamma * rstd, b = beta - mean * a; zero padding after the transform).
 // a, b of the tile's image: computed once per workgroup into a table of 8 * Cin bytes behind the stages (nn_device.h,
-// gn_table_*) and read back per chunk -- 131072 + 8 Cin bytes of LDS in all.
+// gn_table_*) and read back per chunk -- 131072 + 8 Cin bytes of LDS in all (Cin <= 4096), 147456 + 8 Cin with a residual
+// (Cin <= 2048).
 #pragma once
 #include "nn_device.h"   // (already in at file scope: nn_conv3x3.hip includes it before opening its namespace)
 
@@ -29,7 +31,11 @@ constexpr int kWideCK = 32;
 constexpr int kWidePW = 34, kWidePix = 18 * kWidePW;          // 16 x 32 tile + halo = 612 patch pixels
 constexpr int kWidePStage = 2560 * 16;                        // 40960: five rounds of 512 16-byte pieces (2448 used)
 constexpr int kWideWStage = 3 * 128 * kWideCK * 2;            // 24576
-constexpr int kWideLds = 2 * kWidePStage + 2 * kWideWStage;   // 131072
+constexpr int kWideStages = 2 * kWidePStage + 2 * kWideWStage;   // 131072
+// + 16 KB behind the stages for the residual tile of the epilogue (below): with them two rounds of the residual (64 KB) fit
+// behind the patch stages, beside the round in the idle patch stage and the transposition buffer in the other one
+constexpr int kWideRes = 16384;
+constexpr int kWideLds = kWideStages + kWideRes;                 // 147456
 
 // w [Cout][3][3][Cin] bf16 -> per (128-channel block tn, ky, 32-channel chunk c) one contiguous 24 KB slice = the LDS image
 // of that step: [kx 0..2][row 0..127][16-byte chunk pc 0..3][8] = w[tn * 128 + row][ky][kx][c * 32 + (pc ^ key(row)) * 8 + e],
@@ -55,7 +61,9 @@ __global__ __launch_bounds__(256) void conv3x3_wide_weights_kernel(const uint16_
     }
 }
 
-template <bool GN>
+// RES: the launch has a residual and may fetch it by LDS-DMA (below).  Launches without one run the RES = false instantiation:
+// no residual code at all, and the LDS of the stages alone.
+template <bool GN, bool RES>
 __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
     const uint16_t* __restrict__ in, const uint16_t* __restrict__ uw, const uint16_t* __restrict__ bias,
     int bias_img_stride, const uint16_t* __restrict__ residual, uint16_t* __restrict__ out, int Nimg, int H, int W,
@@ -121,7 +129,7 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
     };
     const uint32_t sP_off = (uint32_t)(uintptr_t)sP;
     // GN: scale / shift of every channel of the tile's image, computed once into the table behind the stages (nn_device.h)
-    const uint32_t tab_off = (uint32_t)(uintptr_t)(smem + kWideLds);
+    const uint32_t tab_off = (uint32_t)(uintptr_t)(smem + (RES ? kWideLds : kWideStages));   // (behind the residual rounds)
     auto storeP = [&](int buf, int c, int i0, int i1) {
         float sc[8], sh[8];
         gn_table_read(tab_off, c * (kWideCK / 8) + (tid & 3), sc, sh);
@@ -175,6 +183,30 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
     for (int a = 0; a < 2; a++) a_rd[a] = (uint32_t)((wc * 64 + a * 32 + fn) * 64);
     const uint32_t a_key = (uint32_t)((fn >> 2) & 3);
 
+    // ---- residual tile by LDS-DMA (res_tile_* in nn_conv3x3.hip).  A round = one (column half bh, channel block a) pass of
+    // the epilogue, 4 KB per wave, r = 2 bh + a.  Taken by FULL tiles only (every pixel inside the image, all 128 channels below
+    // Cout) of a residual tensor below 4 GiB (32-bit buffer range); every other tile keeps the per-lane loads.
+    //   round 0: issued in the last chunk's first step into the patch stage that is idle then (nothing is loaded for chunk
+    //            kc; with kc = 1 that is the first step), landed under the step's MFMAs: awaited by the next step's vmcnt(0);
+    //   rounds 1, 2: issued after the barrier that ends the K loop, into the filter stages and the 16 KB behind them;
+    //   round 3: into round 0's slot once round 0 has read it.
+    // The transposition buffer of these tiles lies in the LAST chunk's patch stage (dead after that barrier), not in stage 0.
+    const bool dma = RES && residual != nullptr && tyi * 16 + 16 <= H && txi * 32 + 32 <= W && n0 + 128 <= Cout &&
+                     (uint64_t)Nimg * (uint64_t)(H * W) * (uint64_t)Cout * 2u < (1ull << 32);
+    const uint32_t res_pix = (uint32_t)Cout * 2u, res_row = (uint32_t)W * res_pix;
+    const __amdgpu_buffer_rsrc_t rs_res = buffer_rsrc(residual, (uint32_t)Nimg * (uint32_t)(H * W) * res_pix);
+    auto res_slot = [&](int r) -> char* {
+        if (r == 0 || r == 3) return sP + (kc & 1) * kWidePStage + wave * kResRound;
+        return smem + 2 * kWidePStage + (r - 1) * (8 * kResRound) + wave * kResRound;
+    };
+    auto issueR = [&](int r) {
+        uint32_t off[2];
+        res_tile_lane(lane, res_pix, res_row, off);
+        const uint32_t base = (uint32_t)((nimg * H + tyi * 16 + 4 * wr) * W + txi * 32 + 16 * (r >> 1)) * res_pix +
+                              (uint32_t)(n0 + wc * 64 + (r & 1) * 32) * 2u;
+        res_tile_issue(rs_res, off, base, 2u * res_row, res_slot(r));
+    };
+
     const int nsteps = 3 * kc;
     if (GN) {
         gn_table_fill(tab_off, tid, THREADS, Cin, G, nimg, mean_rstd, gamma, beta);
@@ -201,6 +233,8 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
                 } else if (ky == 0) {
                     issueP((c + 1) & 1, c + 1);
                 }
+            } else if (ky == 0 && dma) {
+                issueR(0);      // every wave has left chunk kc - 2: its stage is free
             }
             const char* pw = sW + bufW * kWideWStage;
 #pragma unroll 1
@@ -236,6 +270,43 @@ __global__ __launch_bounds__(512) void conv3x3_wide_kernel(
     // tiles * 16 rows of {sum, sum of squares} over 32 pixels each -- (H / 16) * (W / 32) * 16 = the (H / 16) * (W / 16) * 8 rows
     // of the 16 x 16-pixel kernels, so gd_nn_groupnorm_finish_partials and the callers' buffers are unchanged
     __syncthreads();
+    if (dma) {
+        // Bias of the lane's eight channel quads FIRST: vmcnt retires in order, a bias load behind a residual DMA would wait
+        // for it.  LDS accesses of this path are inline asm (see res_tile_read); the waits on the DMAs are counted by hand:
+        // a round waits until only the DMAs issued after its own may be outstanding (stores issued in between only make the
+        // wait stricter).
+        const uint32_t tr_off = (uint32_t)(uintptr_t)(sP + ((kc - 1) & 1) * kWidePStage + wave * kTrWave);
+        const uint16_t* bias_d = bias ? bias + (size_t)nimg * bias_img_stride : nullptr;
+        uint2 bb[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                bb[a][q] = bias_d ? *(const uint2*)(bias_d + n0 + wc * 64 + a * 32 + 8 * q + 4 * fk) : make_uint2(0u, 0u);
+        asm volatile("" ::: "memory");
+        issueR(1);
+        issueR(2);
+        ResTile t;
+        t.out = out; t.Cout = Cout;
+        t.stat_rows = ((H + 15) / 16) * ((W + 15) / 16) * 8;
+        t.stat_img = stat_part ? stat_part + (size_t)nimg * (Cout >> 2) * t.stat_rows * 2 : nullptr;
+        const int t16x = (W + 15) / 16;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int bh = r >> 1, a = r & 1;
+            if (r == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");        // rounds 2 and 3 may be in flight
+            else if (r == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // round 3
+            else if (r == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // the 16-column half (txi, bh) IS tile 2 txi + bh of the 16 x 16-pixel kernels' grid: same eight rows per tile
+            const int cx = 2 * txi + bh;
+            t.pix0 = ((size_t)nimg * H + (tyi * 16 + 4 * wr)) * W + (txi * 32 + 16 * bh);
+            t.stat_row = (tyi * t16x + cx) * 8 + wr * 2;
+            t.stat_ok = cx < t16x;
+            res_round(acc[a][2 * bh], acc[a][2 * bh + 1], bb[a], (uint32_t)(uintptr_t)res_slot(r), tr_off, lane, t,
+                      n0 + wc * 64 + a * 32, PatchPix{W}, [&] { if (r == 0) issueR(3); });      // round 0's slot has been read
+        }
+        return;
+    }
     char* tr = smem + wave * kTrWave;
     const uint16_t* bias_n = bias ? bias + (size_t)nimg * bias_img_stride : nullptr;
     const int stat_rows = ((H + 15) / 16) * ((W + 15) / 16) * 8;

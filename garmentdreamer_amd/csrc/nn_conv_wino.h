@@ -105,7 +105,8 @@ __global__ __launch_bounds__(256) void conv3x3_wino_weights_kernel(const uint16_
 // tile boundaries, the step's LDS-DMA and transform dealt out behind the MFMA groups, fragment reads as inline asm with
 // register double buffering and counted waits, filter slices through registers instead of LDS-DMA, a third filter stage
 // fetched two steps ahead -- each 0...-15 %.
-template <bool GN>
+// RES: the launch has a residual and may fetch it by LDS-DMA (epilogue); launches without one run RES = false.
+template <bool GN, bool RES>
 __global__ __launch_bounds__(512) void conv3x3_wino_kernel(
     const uint16_t* __restrict__ in, const uint16_t* __restrict__ uw, const uint16_t* __restrict__ bias,
     int bias_img_stride, const uint16_t* __restrict__ residual, uint16_t* __restrict__ out, int Nimg, int H, int W,
@@ -362,6 +363,51 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(
     // ---- epilogue: bias (+ residual), one rounding, stores through a wave-private LDS transposition buffer
     // (64 contiguous bytes per pixel and instruction), optional GroupNorm partial sums of the stored values
     char* tr = smem + wave * kTrWave;
+    // Residual tile by LDS-DMA (res_tile_* in nn_conv3x3.hip) for FULL tiles (every pixel inside the image, all 128 channels
+    // below Cout) of a residual tensor below 4 GiB; every other tile keeps the per-lane loads below.  Two rounds per wave (a =
+    // 0, 1), 4 KB each, behind the transposition buffers.  Both are issued HERE, not under the K loop: the partner exchange
+    // above writes 128 KB of the 157 KB, so no 32 KB of LDS survive from the last chunk to this point.  What is gained is the
+    // shape of the read (16 pixels x 64 contiguous bytes per instruction, one wait per round) -- the per-lane loads wait for
+    // every 8-byte load in turn, because the compiler cannot tell the plain LDS store that follows each from a DMA target.
+    if (RES && residual != nullptr && tyi * 16 + 16 <= H && txi * 16 + 16 <= W && n0 + BN <= Cout && (Cout & 7) == 0 &&
+        (uint64_t)Nimg * (uint64_t)(H * W) * (uint64_t)Cout * 2u < (1ull << 32)) {
+        const uint32_t res_pix = (uint32_t)Cout * 2u, res_row = (uint32_t)W * res_pix;
+        const __amdgpu_buffer_rsrc_t rs_res = buffer_rsrc(residual, (uint32_t)Nimg * (uint32_t)(H * W) * res_pix);
+        const uint16_t* bias_d = bias ? bias + (size_t)nimg * bias_img_stride : nullptr;
+        uint2 bb[2][4];      // bias first: vmcnt retires in order, a bias load behind a DMA would wait for it
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                bb[a][q] = bias_d ? *(const uint2*)(bias_d + n0 + wc * 64 + a * 32 + 8 * q + 4 * fk) : make_uint2(0u, 0u);
+        asm volatile("" ::: "memory");
+        // the wave's block: rows wq * 8 .. + 7, every second column from pp; pixel P = b * 32 + fn = row 4 b + (fn >> 3),
+        // column 2 (fn & 7) + pp; DMA instruction i moves pixels 16 i .. 16 i + 15 = rows 2 i, 2 i + 1
+        const uint32_t lane_off = (uint32_t)(lane >> 5) * res_row + (uint32_t)(2 * ((lane >> 2) & 7)) * res_pix +
+                                  (uint32_t)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
+        const uint32_t base = (uint32_t)((nimg * H + tyi * 16 + wq * 8) * W + txi * 16 + pp) * res_pix + (uint32_t)(n0 + wc * 64) * 2u;
+        char* slot = smem + 8 * kTrWave + wave * (2 * kResRound);
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                bload_lds16(rs_res, lane_off, base + (uint32_t)(2 * i) * res_row + (uint32_t)(a * 64), slot + a * kResRound + i * 1024);
+        ResTile t;
+        t.out = out; t.Cout = Cout;
+        t.pix0 = ((size_t)nimg * H + (tyi * 16 + wq * 8)) * W + txi * 16 + pp;
+        t.stat_rows = tpi * 8;
+        t.stat_img = stat_part ? stat_part + (size_t)nimg * (Cout >> 2) * t.stat_rows * 2 : nullptr;
+        t.stat_row = (tyi * tiles_x + txi) * 8 + (pp * 2 + wq) * 2;
+        t.stat_ok = true;
+        const auto pix_of = [W](int pr) { return ((pr >> 5) * 4 + ((pr & 31) >> 3)) * W + 2 * (pr & 7); };
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // round 1 may be in flight
+        res_round(acc[0][0][0], acc[0][0][1], bb[0], (uint32_t)(uintptr_t)slot, (uint32_t)(uintptr_t)tr, lane, t, n0 + wc * 64,
+                  pix_of, [] {});
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        res_round(acc[0][1][0], acc[0][1][1], bb[1], (uint32_t)(uintptr_t)(slot + kResRound), (uint32_t)(uintptr_t)tr, lane, t,
+                  n0 + wc * 64 + 32, pix_of, [] {});
+        return;
+    }
     bool ok[2];
     size_t opix[2];
 #pragma unroll

@@ -34,3 +34,20 @@ for (N, ci, co, hw, res) in SH:
         td, tw, tz = timeit(fd), timeit(fw), timeit(fz)
         td, tw, tz = min(td, timeit(fd)), min(tw, timeit(fw)), min(tz, timeit(fz))
     print(f"N{N} {ci}->{co} @{hw} res={res}: direct {td*1e6:7.1f}us | wino {tw*1e6:7.1f}us {td/tw:4.2f}x | wide {tz*1e6:7.1f}us {td/tz:4.2f}x", flush=True)
+    del x, w, r, y, part
+
+# Plain conv2 launches of the step that carry a residual on the Winograd kernel (GroupNorm by its own kernel before them): the
+# VAE encoder's 128^2 and 64^2 levels (V images) and the UNet's ResnetBlock2D levels (2 V latents), with and without residual.
+PLAIN = [(V, 512, 512, 128), (V, 512, 512, 64), (2 * V, 320, 320, 64), (2 * V, 640, 640, 32), (2 * V, 1280, 1280, 16)]
+for (N, ci, co, hw) in PLAIN:
+    if not L.gd_nn_conv3x3_wino_supported(N, hw, hw, ci, co):
+        continue
+    x = torch.randn(N, ci, hw, hw, device="cuda").to(torch.bfloat16).contiguous(memory_format=cl)
+    w = (torch.randn(co, ci, 3, 3, device="cuda") / (3 * ci ** 0.5)).to(torch.bfloat16).contiguous(memory_format=cl)
+    b = torch.randn(co, device="cuda").to(torch.bfloat16)
+    r = torch.randn(N, co, hw, hw, device="cuda").to(torch.bfloat16).contiguous(memory_format=cl)
+    with torch.no_grad():
+        t1, t0 = timeit(lambda: nn_ops._wino_launch(x, w, b, r, co)), timeit(lambda: nn_ops._wino_launch(x, w, b, None, co))
+        t1, t0 = min(t1, timeit(lambda: nn_ops._wino_launch(x, w, b, r, co))), min(t0, timeit(lambda: nn_ops._wino_launch(x, w, b, None, co)))
+    print(f"N{N} {ci}->{co} @{hw} plain wino: res=1 {t1*1e6:7.1f}us | res=0 {t0*1e6:7.1f}us | cost {(t1-t0)*1e6:6.1f}us", flush=True)
+    del x, w, r

@@ -9,7 +9,9 @@ process loads both sets and asserts ``torch.equal`` (equal digests) case by case
 gd_nn_conv3x3_gn_forward_stats, gd_nn_conv3x3_wino_gn_forward (the persistent streaming kernel has no GroupNorm entry:
 every GroupNorm launch of the patch path runs conv3x3_gn_patch_kernel).  Shapes: those of
 tests/test_conv_gn_table_gpu.py, and the GroupNorm-fused launches of the VAE encoder in one 8-view SDS step (four
-128 -> 128 @512^2, one 128 -> 256 and three 256 -> 256 @256^2; with and without residual), outputs and statistics.
+128 -> 128 @512^2, one 128 -> 256 and three 256 -> 256 @256^2; with and without residual), outputs and statistics.  The
+last field of a case tells whether the GroupNorm loader is on: the plain wide-tile and Winograd entries run the same
+epilogues (PLAIN below).
 """
 import hashlib
 import os
@@ -30,7 +32,12 @@ SMALL = [(k, 2, c, 64, 20, 40, 0, 0, 1) for k, cs in (("wide", (64, 128, 160, 32
 VAE = [(k, 8, 128, 128, 512, 512, r, 1, 1) for k in ("wide", "patch", "wino") for r in (1, 0)] + \
       [(k, 8, 128, 256, 256, 256, 0, 1, 1) for k in ("patch", "wino")] + \
       [(k, 8, 256, 256, 256, 256, r, 1, 1) for k in ("patch", "wino") for r in (1, 0)]
-CASES = SMALL + VAE
+# the same entries' plain twins (no GroupNorm in the loader), which share the epilogues: ragged test shapes, and the plain
+# conv2 launches of the step that carry a residual (VAE 128^2 / 64^2 levels, UNet levels at 2 x 8 latents)
+PLAIN = [(k, 2, 96, 320, 20, 40, r, 1, 0) for k in ("wide", "wino") for r in (1, 0)] + \
+        [("wino", n, c, c, hw, hw, r, 0, 0) for (n, c, hw) in ((8, 512, 128), (8, 512, 64), (16, 320, 64), (16, 640, 32),
+                                                                 (16, 1280, 16)) for r in (1, 0)]
+CASES = [c + (1,) for c in SMALL + VAE] + [c + (0,) for c in PLAIN]
 
 
 def child(lib_path, out_dir):
@@ -38,7 +45,7 @@ def child(lib_path, out_dir):
     nn_ops.use_library(lib_path)
     L = nn_ops.lib()
     dev = "cuda:0"
-    for i, (kind, N, Cin, Cout, H, W, res, stats, silu) in enumerate(CASES):
+    for i, (kind, N, Cin, Cout, H, W, res, stats, silu, gn) in enumerate(CASES):
         g = torch.Generator(dev).manual_seed(1000 + i)
         x = torch.randn(N, Cin, H, W, device=dev, generator=g) * 1.5 + 0.3
         n = torch.arange(N, device=dev, dtype=torch.float32).view(N, 1, 1, 1)
@@ -55,10 +62,10 @@ def child(lib_path, out_dir):
         part = torch.zeros(N * (Cout // 4) * rows * 2, dtype=torch.float32, device=dev) if stats else None
         out = {}
         with torch.no_grad():
-            out["y"] = nn_ops._tiled_launch(kind, x, w, b, r, Cout, part, (mr, gw, gb, 32, silu))
+            out["y"] = nn_ops._tiled_launch(kind, x, w, b, r, Cout, part, (mr, gw, gb, 32, silu) if gn else None)
             if stats:
                 out["part"] = part
-            if kind == "patch" and not stats:      # gd_nn_conv3x3_gn_forward itself (_tiled_launch calls the _stats entry)
+            if kind == "patch" and not stats and gn:      # gd_nn_conv3x3_gn_forward itself (_tiled_launch calls the _stats entry)
                 y2 = torch.empty_like(out["y"])
                 st = torch.cuda.current_stream().cuda_stream
                 ret = L.gd_nn_conv3x3_gn_forward(st, x.data_ptr(), mr.data_ptr(), gw.data_ptr(), gb.data_ptr(), 32, silu,
