@@ -32,6 +32,7 @@ RASTER_SOURCES = [
     ("raster_template.hip", ["-ffp-contract=off"]),   # d2 is compared bit for bit with an fp32 numpy statement
     ("raster_mesh.hip", ["-ffp-contract=off"]),       # rast / wts likewise (tests/mesh_reference.py)
     ("raster_geometry.hip", ["-ffp-contract=off"]),   # include/gd_mesh_geometry.h fixes the order of every operation
+    ("raster_remesh.hip", ["-ffp-contract=off"]),     # include/gd_mesh_remesh.h likewise (tests/remesh_reference.py)
     ("raster_gbuffer_losses.hip", ["-ffp-contract=off"]),   # include/gd_mesh_losses.h likewise
     ("raster_fit.hip", ["-ffp-contract=off"]),        # include/gd_fit.h likewise (tests/fit_reference.py)
     ("raster_texture.hip", ["-ffp-contract=off"]),    # the encoding likewise (include/gd_texture.h, tests/texture_reference.py)

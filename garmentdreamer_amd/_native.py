@@ -135,6 +135,54 @@ MESH_GEOMETRY_SIGNATURES = {
     "gd_mesh_normal_consistency_backward": (_i, [_vp] + [_i] * 2 + [_vp] * 4),     # stream, F P, fn face_nbr dloss dfn
 }
 
+# the deformer's remesher: connectivity, split, collapse and flip rounds, relax, project (include/gd_mesh_remesh.h)
+REMESH_FLAG_INDEX, REMESH_FLAG_REPEATED, REMESH_FLAG_NONMANIFOLD, REMESH_FLAG_CAPACITY = 0, 1, 2, 3
+REMESH_FLAG_SELECTED, REMESH_FLAG_UNPROJECTED, REMESH_FLAGS = 4, 5, 8
+REMESH_MAX_CELLS = 1 << 21
+
+
+class RemeshMesh(C.Structure):
+    """``gd_remesh_mesh``, passed by pointer"""
+    _fields_ = [("V", C.c_int32), ("F", C.c_int32), ("E", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "verts", "tri", "ev", "eh", "bnd", "nbr_ptr", "nbr_idx", "vf_ptr", "vf_idx")]
+
+
+class RemeshGrid(C.Structure):
+    """``gd_remesh_grid``, passed by pointer"""
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int32 * 3)]
+
+
+_RM = C.POINTER(RemeshMesh)
+_RG = C.POINTER(RemeshGrid)
+MESH_REMESH_SIGNATURES = {
+    "gd_mesh_remesh_scan": (_i, [_vp, _i, _vp, _vp]),                              # stream, n, in out
+    "gd_mesh_remesh_keys": (_i, [_vp, _i, _i] + [_vp] * 4),                        # stream, V F, tri hkeys ckeys flags
+    "gd_mesh_remesh_heads": (_i, [_vp, _i] + [_vp] * 3),                           # stream, n, sorted head flags
+    "gd_mesh_remesh_edge_tables": (_i, [_vp] + [_i] * 3 + [_vp] * 10),             # stream, V F E, sorted order scan fe ev eh
+                                                                                   # ukeys rkeys bnd flags
+    "gd_mesh_remesh_vertex_tables": (_i, [_vp] + [_i] * 3 + [_vp] * 7),            # ..., ukeys srkeys sckeys nbr_ptr nbr_idx
+                                                                                   # vf_ptr vf_idx
+    "gd_mesh_remesh_split_mark": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp]),           # stream, V E, verts ev, hi2, mark
+    "gd_mesh_remesh_split_count": (_i, [_vp, _i, _i] + [_vp] * 3),                 # stream, F E, fe mark count
+    "gd_mesh_remesh_split_apply": (_i, [_vp] + [_i] * 5 + [_vp] * 10),             # stream, V F E Vcap Fcap, verts tri ev fe
+                                                                                   # mark escan fscan verts_out tri_out flags
+    "gd_mesh_remesh_collapse_candidates": (_i, [_vp, _RM, _f, _f] + [_vp] * 3),    # stream, mesh, lo2 hi2, dir ekey vkey
+    "gd_mesh_remesh_collapse_select": (_i, [_vp, _RM] + [_vp] * 5),                # stream, mesh, dir ekey vkey remap flags
+    "gd_mesh_remesh_relabel": (_i, [_vp, _i, _i] + [_vp] * 5),                     # stream, V F, tri remap tri_out alive flags
+    "gd_mesh_remesh_compact_faces": (_i, [_vp, _i, _i] + [_vp] * 5),               # stream, F Fcap, tri alive scan out flags
+    "gd_mesh_remesh_flip_candidates": (_i, [_vp, _RM] + [_vp] * 3),                # stream, mesh, quad ekey vkey
+    "gd_mesh_remesh_flip_apply": (_i, [_vp] + [_i] * 3 + [_vp] * 6),               # stream, V F E, eh quad ekey vkey tri flags
+    "gd_mesh_remesh_relax": (_i, [_vp, _RM, _vp, _vp]),                            # stream, mesh, verts_out moved
+    "gd_mesh_remesh_grid_bin": (_i, [_vp, _RG, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),  # stream, grid, V F, verts tri,
+                                                                                   # scatter, count start items, capacity, flags
+    "gd_mesh_remesh_project": (_i, [_vp, _RG, _i, _vp, _vp, _i, _i] + [_vp] * 4 + [_i, _vp, _vp]),  # stream, grid, n, points
+                                                              # moved, V F, verts tri start items, capacity, out flags
+    "gd_mesh_remesh_used_vertices": (_i, [_vp, _i, _i] + [_vp] * 3),               # stream, V F, tri used flags
+    "gd_mesh_remesh_compact_vertices": (_i, [_vp] + [_i] * 3 + [_vp] * 7),         # stream, V F Vcap, verts tri used scan
+                                                                                   # verts_out tri_out flags
+    "gd_mesh_remesh_edge_lengths": (_i, [_vp, _i, _i] + [_vp] * 3),                # stream, V E, verts edges len
+}
+
 # the second stage's G-buffer losses: enhanced / plain normal map and hole mask, one view per call (include/gd_mesh_losses.h)
 MESH_LOSS_ENHANCED, MESH_LOSS_PLAIN, MESH_LOSS_HOLE = 1, 2, 4
 MESH_LOSS_STATS_WORDS = 6
@@ -256,6 +304,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
+                + list(MESH_REMESH_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface

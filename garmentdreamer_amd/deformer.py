@@ -4,13 +4,13 @@ First stage (the loop over ``progress_bar_first``, ``Deformer.step``): Adam on v
 normal-consistency loss and the uniform Laplacian loss, on the HIP kernels of ``mesh_deform`` (render) and ``mesh_geometry``
 (normals and the two geometry losses).
 
-Second stage (the loop over ``progress_bar_second``, ``begin_second_stage`` / ``step_second`` / ``adopt_remesh``): the same
+Second stage (the loop over ``progress_bar_second``, ``begin_second_stage`` / ``step_second`` / ``remesh``): the same
 three terms plus the normal-map loss and the hole-mask loss against a frozen copy of the mesh, on the kernels of
 ``mesh_losses``, under the visible-rows update ``lr g / (|g| + eps)``; with a ``neural_shader.NeuralShader`` also the
-``shading`` loss (``mesh_losses.shading_loss``) and the shader's own Adam.  No CPU path anywhere.
+``shading`` loss (``mesh_losses.shading_loss``) and the shader's own Adam; at an upsample iteration ``remesh`` remeshes
+the current mesh on the kernels of ``mesh_remesh`` and ``adopt_remesh`` carries on from the result.  No CPU path anywhere.
 
-Out of scope here: remeshing itself (``adopt_remesh`` takes the remeshed mesh), reading the views, the space normalisation
-and the image dumps.
+Out of scope here: reading the views, the space normalisation and the image dumps.
 """
 from __future__ import annotations
 
@@ -20,6 +20,7 @@ import torch
 
 from . import mesh_geometry as mg
 from . import mesh_losses as ml
+from . import mesh_remesh as mr
 from ._launch import require_gpu
 from .flat_adam import FlatAdam
 from .mesh_deform import GBufferRenderer
@@ -187,6 +188,19 @@ class Deformer:
         out = {k: v.detach() for k, v in losses.items()}
         out["total"] = total.detach()
         return out
+
+    def remesh(self, h: Optional[float] = None) -> Dict[str, list]:
+        """An upsample iteration (deformation.py:273-295): remesh the current mesh ``initial + offsets`` towards edge
+        length ``h`` (default: half its mean edge length, as the reference) with ``mesh_remesh.remesh_botsch`` and continue
+        on the result through ``adopt_remesh``.  Returns the remesher's ``info``.  Reads counts back from the GPU."""
+        if not hasattr(self, "views"):
+            raise RuntimeError("Deformer.remesh: call begin_second_stage first")
+        vertices = (self.initial + self.offsets).detach()
+        if h is None:
+            h = 0.5 * float(mr.mean_edge_length(vertices, self.geometry))
+        new_vertices, new_indices, info = mr.remesh_botsch(vertices, self.geometry.tri, h)
+        self.adopt_remesh(new_vertices, new_indices)
+        return info
 
     def adopt_remesh(self, vertices: torch.Tensor, indices: torch.Tensor) -> None:
         """Continue the second stage on a remeshed surface (deformation.py:273-295; the remeshing itself is the caller's):

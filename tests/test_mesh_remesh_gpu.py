@@ -1,0 +1,256 @@
+"""GPU checks of the remesher (garmentdreamer_amd/mesh_remesh.py, the entries of include/gd_mesh_remesh.h in
+csrc/raster_remesh.hip) and of ``Deformer.remesh`` against the numpy statement of tests/remesh_reference.py.
+
+Discrete results (the faces after a split, one collapse round, one flip round) must EQUAL the float64 statement's: the CPU
+test pins meshes on which every comparison is decided by a relative margin of at least 1e-5, some thirty times the fp32
+rounding of the compared quantities.  Positions (relax, project) follow the 4x rule of test_mesh_geometry_gpu._check: the
+GPU's normalised error against the float64 statement is at most four times that of the float32 statement.  A whole remesh is
+held to the hard invariants, to the distance from the input surface and to the statement's quality less QUALITY_MARGIN.
+
+Meshes: a single triangle, a two-triangle quad, the jittered 10 x 10 cloth, the jittered tube(24, 12) (2 304 faces after one
+split: several workgroups per kernel), the stretched closed sphere (128 faces), and the cloth with one unreferenced vertex."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import remesh_reference as rr
+from tests.test_mesh_geometry_gpu import _check, _deformer
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _gpu_mesh(v, tri):
+    return _dev(v.astype(np.float32)), _dev(tri.astype(np.int32))
+
+
+def _mr():
+    from garmentdreamer_amd import mesh_remesh as mr
+    return mr
+
+
+@functools.lru_cache(maxsize=None)
+def _mesh(name, factor):
+    """(float32 vertices, triangles, h); shared and read-only"""
+    v, tri = rr.mesh(name)
+    return v, tri, factor * rr.mean_edge_length(*rr.compact_vertices(v, tri))
+
+
+# ---- single passes ----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", rr.MESHES)
+def test_split_equals_the_statement(name):
+    v, tri, h = _mesh(name, 0.5)
+    v64, t64, n64 = rr.split(v.astype(np.float64), tri, h)
+    v32, _, _ = rr.split(v, tri, h)
+    gv, gt, n = _mr().split_long_edges(*_gpu_mesh(v, tri), h)
+    print(name, "split edges", n, "faces", tri.shape[0], "->", gt.shape[0])
+    assert n == n64 and n > 0
+    assert gt.dtype == torch.int32 and np.array_equal(gt.cpu().numpy(), t64)
+    assert gv.shape[0] == v.shape[0] + n
+    assert np.array_equal(gv.cpu().numpy().view(np.uint32), v32.view(np.uint32))       # 0.5f (a + b), bit for bit
+
+
+@pytest.mark.parametrize("name,factor", [("single", 1.5), ("quad", 1.5), ("cloth", 1.5), ("tube", 1.4), ("sphere", 0.5),
+                                         ("cloth_extra", 1.5)])
+def test_one_collapse_round_equals_the_statement(name, factor):
+    v, tri, _ = _mesh(name, factor)
+    h = 1.5 * rr.mean_edge_length(*rr.compact_vertices(v, tri))
+    t64, n64 = rr.collapse_round(v.astype(np.float64), tri, h)
+    gt, n = _mr().collapse_short_edges_round(*_gpu_mesh(v, tri), h)
+    print(name, "collapsed", n, "faces", tri.shape[0], "->", gt.shape[0])
+    assert n == n64 and (n > 0 or name in ("single", "quad"))
+    assert np.array_equal(gt.cpu().numpy(), t64)
+
+
+def test_one_flip_round_equals_the_statement():
+    v, tri = rr.flip_test_mesh()
+    t64, n64 = rr.flip_round(v.astype(np.float64), tri)
+    gt, n = _mr().flip_edges_round(*_gpu_mesh(v, tri))
+    print("flipped", n, "of", tri.shape[0], "faces")
+    assert n == n64 and n > 0
+    assert np.array_equal(gt.cpu().numpy(), t64)
+
+
+@pytest.mark.parametrize("name", ["cloth", "tube", "sphere"])
+def test_relax_and_project_against_the_float64_statement(name):
+    mr = _mr()
+    v, tri, h = _mesh(name, 0.5)
+    sv, stri = rr.compact_vertices(v, tri)
+    v1, t1, _ = rr.split(sv, stri, h)                                           # float32: what the GPU gets
+    r64, moved64 = rr.relax(v1.astype(np.float64), t1)
+    r32, _ = rr.relax(v1, t1)
+    gv, gmoved = mr.tangential_relax(*_gpu_mesh(v1, t1))
+    assert np.array_equal(gmoved.cpu().numpy().astype(bool), moved64) and moved64.any()
+    _check(f"{name} relax", gv.cpu().numpy(), r64, r32)
+    cell = rr.cell_size(sv, stri, h)
+    p64, left64 = rr.project(r32.astype(np.float64), moved64, sv.astype(np.float64), stri, cell)   # all triangles
+    p32, _ = rr.project(r32, moved64, sv, stri, cell)
+    surface = mr.build_surface_grid(*_gpu_mesh(sv, stri), min_cell=4.0 / 3.0 * h)
+    gp, left = mr.project_to_surface(_dev(r32), surface, _dev(moved64.astype(np.int32)))
+    assert left == 0 and left64 == 0
+    _check(f"{name} project", gp.cpu().numpy(), p64, p32)
+    gall, left = mr.project_to_surface(_dev(r32), surface)                      # no mask: every vertex is a query
+    assert left == 0
+    _check(f"{name} project all", gall.cpu().numpy(), rr.closest_on_surface(r32.astype(np.float64), sv.astype(np.float64), stri)[0],
+           rr.closest_on_surface(r32, sv, stri)[0])
+
+
+# ---- the whole remesh -------------------------------------------------------------------------------------------------------
+
+WHOLE = [(name, 0.5) for name in rr.MESHES] + [("tube", 1.4), ("cloth", 1.5)]
+
+
+@functools.lru_cache(maxsize=None)
+def _statement(name, factor):
+    v, tri, h = _mesh(name, factor)
+    out = {}
+    for dtype in (np.float64, np.float32):
+        v2, t2, info, _ = rr.remesh(v, tri, h, dtype=dtype)
+        out[dtype] = (v2, t2, info)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _gpu_remesh(name, factor, iterations=10):
+    v, tri, h = _mesh(name, factor)
+    gv, gt, info = _mr().remesh_botsch(*_gpu_mesh(v, tri), h, iterations=iterations)
+    return gv, gt, info
+
+
+def _surface_distance(v, sv, stri):
+    return float(np.sqrt(rr.closest_on_surface(v.astype(np.float64), sv.astype(np.float64), stri)[1].max()))
+
+
+@pytest.mark.parametrize("name,factor", WHOLE)
+def test_whole_remesh(name, factor):
+    mr = _mr()
+    v, tri, h = _mesh(name, factor)
+    sv, stri = rr.compact_vertices(v, tri)
+    gv, gt, info = _gpu_remesh(name, factor)
+    assert gv.dtype == torch.float32 and gt.dtype == torch.int32 and gv.is_cuda and gt.is_cuda
+    assert sorted(info) == ["collapsed", "flipped", "split", "unprojected"]
+    assert all(len(x) == 10 and all(type(n) is int for n in x) for x in info.values())
+    out_v, out_t = gv.cpu().numpy(), gt.cpu().numpy().astype(np.int64)
+    chi, loops = rr.invariants(out_v, out_t)                # <= 2 faces per edge, no repeated vertex, no duplicate face,
+    chi0, loops0 = rr.invariants(sv, stri)                  # every vertex referenced, consistent orientation, finite
+    print(f"{name} x{factor}: faces {tri.shape[0]} -> {out_t.shape[0]}, Euler {chi0} -> {chi}, loops {loops0} -> {loops}, info {info}")
+    assert (chi, loops) == (chi0, loops0)
+    assert sum(info["unprojected"]) == 0
+    # no edge above hi right after the last split: nine iterations, then the single pass
+    v9, t9, info9 = _gpu_remesh(name, factor, 9)
+    v10, t10, n10 = mr.split_long_edges(v9, t9, h)
+    assert n10 == info["split"][9] and {k: x[:9] for k, x in info.items()} == info9
+    p = v10.cpu().numpy()
+    e = rr.Connectivity(t10.cpu().numpy(), p.shape[0]).ev
+    lo2, hi2 = rr.thresholds(h, np.float32)
+    longest2 = rr.sqlen(p[e[:, 0]], p[e[:, 1]]).max()
+    print(f"   longest edge after the last split {np.sqrt(longest2) / h:.4f} h, hi = {4 / 3:.4f} h")
+    assert longest2 <= hi2
+    # distance from the input surface
+    ref = _statement(name, factor)
+    d64 = _surface_distance(ref[np.float64][0], sv, stri)
+    d32 = _surface_distance(ref[np.float32][0], sv, stri)
+    d = _surface_distance(out_v, sv, stri)
+    print(f"   distance from the input surface: GPU {d:.3e}, float64 statement {d64:.3e}, float32 statement {d32:.3e}")
+    assert d <= d64 + 4 * d32
+    # quality
+    share64, valence64 = rr.quality(ref[np.float64][0], ref[np.float64][1], h)
+    share, valence = rr.quality(out_v, out_t, h)
+    print(f"   in-band share GPU {share:.4f}, statement {share64:.4f}; mean |valence - target| GPU {valence:.4f}, statement "
+          f"{valence64:.4f}; margins {rr.QUALITY_MARGIN}")
+    assert share >= share64 - rr.QUALITY_MARGIN["share"]
+    assert valence <= valence64 + rr.QUALITY_MARGIN["valence"]
+
+
+def test_two_runs_are_bit_identical():
+    v, tri, h = _mesh("tube", 0.5)
+    first = _gpu_remesh("tube", 0.5)
+    gv, gt, info = _mr().remesh_botsch(*_gpu_mesh(v, tri), h)
+    assert torch.equal(gv.view(torch.int32), first[0].view(torch.int32)) and torch.equal(gt, first[1]) and info == first[2]
+
+
+@pytest.mark.parametrize("name", ["single", "quad"])
+def test_a_large_target_leaves_a_tiny_mesh_unchanged(name):
+    v, tri, _ = _mesh(name, 0.5)
+    gv, gt, info = _mr().remesh_botsch(*_gpu_mesh(v, tri), 10.0)
+    assert np.array_equal(gv.cpu().numpy().view(np.uint32), v.view(np.uint32)) and np.array_equal(gt.cpu().numpy(), tri)
+    assert sum(info["split"]) == sum(info["collapsed"]) == sum(info["flipped"]) == 0
+
+
+def test_a_non_manifold_fan_is_refused_before_any_apply_kernel(monkeypatch):
+    mr = _mr()
+    v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1]], dtype=np.float32)
+    tri = np.array([[0, 1, 2], [1, 0, 3], [0, 1, 4]], dtype=np.int32)                  # three faces on edge (0, 1)
+    launched = []
+    real = mr.launch
+    monkeypatch.setattr(mr, "launch", lambda name, *a: (launched.append(name), real(name, *a))[1])
+    for call in (lambda: mr.remesh_botsch(_dev(v), _dev(tri), 0.5), lambda: mr.split_long_edges(_dev(v), _dev(tri), 0.5),
+                 lambda: mr.collapse_short_edges_round(_dev(v), _dev(tri), 0.5), lambda: mr.flip_edges_round(_dev(v), _dev(tri))):
+        with pytest.raises(ValueError, match="non-manifold"):
+            call()
+    print("entries launched:", sorted(set(launched)))
+    assert set(launched) == {"gd_mesh_remesh_keys", "gd_mesh_remesh_heads", "gd_mesh_remesh_scan"}
+
+
+def test_bad_meshes_raise_value_errors():
+    mr = _mr()
+    v = _dev(rr.SINGLE[0].astype(np.float32))
+    with pytest.raises(ValueError, match="out of range"):
+        mr.remesh_botsch(v, _dev(np.array([[0, 1, 3]], dtype=np.int32)), 0.5)
+    with pytest.raises(ValueError, match="out of range"):
+        mr.remesh_botsch(v, _dev(np.array([[0, 1, -1]], dtype=np.int64)), 0.5)
+    with pytest.raises(ValueError, match="twice"):
+        mr.remesh_botsch(v, _dev(np.array([[0, 1, 1]], dtype=np.int32)), 0.5)
+    for h in (0.0, -1.0, float("inf"), float("nan")):
+        with pytest.raises(ValueError, match="h must be positive and finite"):
+            mr.remesh_botsch(v, _dev(rr.SINGLE[1].astype(np.int32)), h)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        mr.remesh_botsch(v.cpu(), _dev(rr.SINGLE[1].astype(np.int32)), 0.5)
+    out_v, out_t, info = mr.remesh_botsch(v, _dev(np.zeros((0, 3), dtype=np.int32)), 0.5)
+    assert out_v.shape == (0, 3) and out_t.shape == (0, 3)
+
+
+def test_mean_edge_length():
+    from garmentdreamer_amd import mesh_geometry as mg
+    v, tri, _ = _mesh("tube", 0.5)
+    geo = mg.build_geometry(tri, num_vertices=v.shape[0], device=DEV)
+    got = _mr().mean_edge_length(_dev(v), geo)
+    assert got.is_cuda and got.dim() == 0
+    assert abs(got.item() - rr.mean_edge_length(v, tri)) <= 1e-6 * rr.mean_edge_length(v, tri)
+
+
+# ---- the deformer -----------------------------------------------------------------------------------------------------------
+
+def test_deformer_remesh():
+    from garmentdreamer_amd import deformer as dm
+    d = _deformer()
+    for _ in range(2):
+        d.step([0, 1])
+    n = len(d.mvps)
+    normals = [torch.full((64, 64, 3), 0.5, device=DEV) for _ in range(n)]
+    eye, zero = torch.eye(3, device=DEV), torch.zeros(3, device=DEV)
+    with pytest.raises(RuntimeError, match="begin_second_stage"):
+        d.remesh()
+    d.begin_second_stage(normals, [eye] * n, [zero] * n)
+    faces, lr, weights = d.geometry.tri.shape[0], d.lr, dict(d.second_weights)
+    frozen_v, frozen_t = d.rf_vertices.clone(), d.rf_geometry.tri.clone()
+    info = d.remesh()
+    ratio = d.geometry.tri.shape[0] / faces
+    print("faces", faces, "->", d.geometry.tri.shape[0], "ratio", ratio, "info", info)
+    assert 3.0 <= ratio <= 5.0                                    # h = half the mean edge length: about four times the faces
+    assert sorted(info) == ["collapsed", "flipped", "split", "unprojected"] and sum(info["unprojected"]) == 0
+    assert d.lr == lr * 0.25
+    assert d.second_weights["laplacian"] == 4 * weights["laplacian"]
+    assert d.second_weights["normal_consistency"] == 4 * weights["normal_consistency"]
+    assert d.offsets.shape == d.initial.shape == (d.geometry.num_vertices, 3) and not d.offsets.detach().any()
+    assert torch.equal(d.rf_vertices, frozen_v) and torch.equal(d.rf_geometry.tri, frozen_t)
+    losses = d.step_second([0, 1])
+    assert all(torch.isfinite(x).all() for x in losses.values())
+    assert isinstance(dm.Deformer.remesh.__doc__, str)
