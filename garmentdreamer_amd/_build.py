@@ -33,6 +33,7 @@ RASTER_SOURCES = [
     ("raster_mesh.hip", ["-ffp-contract=off"]),       # rast / wts likewise (tests/mesh_reference.py)
     ("raster_geometry.hip", ["-ffp-contract=off"]),   # include/gd_mesh_geometry.h fixes the order of every operation
     ("raster_remesh.hip", ["-ffp-contract=off"]),     # include/gd_mesh_remesh.h likewise (tests/remesh_reference.py)
+    ("raster_simplify.hip", ["-ffp-contract=off"]),   # include/gd_mesh_simplify.h likewise (tests/simplify_reference.py)
     ("raster_gbuffer_losses.hip", ["-ffp-contract=off"]),   # include/gd_mesh_losses.h likewise
     ("raster_fit.hip", ["-ffp-contract=off"]),        # include/gd_fit.h likewise (tests/fit_reference.py)
     ("raster_texture.hip", ["-ffp-contract=off"]),    # the encoding likewise (include/gd_texture.h, tests/texture_reference.py)

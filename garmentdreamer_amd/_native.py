@@ -183,6 +183,18 @@ MESH_REMESH_SIGNATURES = {
     "gd_mesh_remesh_edge_lengths": (_i, [_vp, _i, _i] + [_vp] * 3),                # stream, V E, verts edges len
 }
 
+# the final mesh's post-process: quadric decimation, Taubin smoothing, rotation (include/gd_mesh_simplify.h); it shares the
+# connectivity, the flags and the compaction entries of the remesher
+MESH_SIMPLIFY_SIGNATURES = {
+    "gd_mesh_simplify_quadrics": (_i, [_vp, _RM, _vp]),                            # stream, mesh, Q
+    "gd_mesh_simplify_candidates": (_i, [_vp, _RM] + [_vp] * 4),                   # stream, mesh, Q key dir cost
+    "gd_mesh_simplify_spread": (_i, [_vp, _RM] + [_vp] * 4),                       # stream, mesh, key threshold lock vkey
+    "gd_mesh_simplify_select": (_i, [_vp, _RM] + [_vp] * 8),                       # stream, mesh, key threshold dir vkey remap
+                                                                                   # Q lock flags
+    "gd_mesh_simplify_smooth": (_i, [_vp, _RM, _f, _vp]),                          # stream, mesh, w, verts_out
+    "gd_mesh_simplify_rotate": (_i, [_vp, _i, _vp, _vp]),                          # stream, V, verts verts_out
+}
+
 # the second stage's G-buffer losses: enhanced / plain normal map and hole mask, one view per call (include/gd_mesh_losses.h)
 MESH_LOSS_ENHANCED, MESH_LOSS_PLAIN, MESH_LOSS_HOLE = 1, 2, 4
 MESH_LOSS_STATS_WORDS = 6
@@ -304,7 +316,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {_LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + list(SCENE_SIGNATURES.items()) + list(MESH_SIGNATURES.items()) \
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
-                + list(MESH_REMESH_SIGNATURES.items()) \
+                + list(MESH_REMESH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface

@@ -8,7 +8,9 @@ Second stage (the loop over ``progress_bar_second``, ``begin_second_stage`` / ``
 three terms plus the normal-map loss and the hole-mask loss against a frozen copy of the mesh, on the kernels of
 ``mesh_losses``, under the visible-rows update ``lr g / (|g| + eps)``; with a ``neural_shader.NeuralShader`` also the
 ``shading`` loss (``mesh_losses.shading_loss``) and the shader's own Adam; at an upsample iteration ``remesh`` remeshes
-the current mesh on the kernels of ``mesh_remesh`` and ``adopt_remesh`` carries on from the result.  No CPU path anywhere.
+the current mesh on the kernels of ``mesh_remesh`` and ``adopt_remesh`` carries on from the result.  ``final_mesh`` is the
+stage's product: the current mesh rotated upright, decimated and smoothed on the kernels of ``mesh_simplify``.  No CPU path
+anywhere.
 
 Out of scope here: reading the views, the space normalisation and the image dumps.
 """
@@ -21,6 +23,7 @@ import torch
 from . import mesh_geometry as mg
 from . import mesh_losses as ml
 from . import mesh_remesh as mr
+from . import mesh_simplify as ms
 from ._launch import require_gpu
 from .flat_adam import FlatAdam
 from .mesh_deform import GBufferRenderer
@@ -201,6 +204,15 @@ class Deformer:
         new_vertices, new_indices, info = mr.remesh_botsch(vertices, self.geometry.tri, h)
         self.adopt_remesh(new_vertices, new_indices)
         return info
+
+    def final_mesh(self, target_faces: int = 40000, smooth: bool = True, rotate: bool = True):
+        """The mesh the stage hands on (``write_mesh(..., 'final_mesh.obj', final_mesh, post_process=True)``,
+        deformation.py's last line): ``mesh_simplify.post_process_mesh`` of the current mesh ``initial + offsets``, as
+        ``(vertices float32 [V',3], indices int32 [F',3])`` for ``mesh_simplify.write_obj``.  Nothing of this object
+        changes.  Reads counts back from the GPU."""
+        vertices = (self.initial + self.offsets).detach()
+        new_vertices, new_indices, _ = ms.post_process_mesh(vertices, self.geometry.tri, target_faces, smooth, rotate)
+        return new_vertices, new_indices
 
     def adopt_remesh(self, vertices: torch.Tensor, indices: torch.Tensor) -> None:
         """Continue the second stage on a remeshed surface (deformation.py:273-295; the remeshing itself is the caller's):
