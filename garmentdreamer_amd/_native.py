@@ -246,6 +246,28 @@ BAKE_SIGNATURES = {
     "gd_bake_last_error": (C.c_char_p, []),
 }
 
+# the chart-based UV atlas of the export: classes, charts, bounds, corners, lost faces (include/gd_atlas.h); messages go
+# through gd_mesh_last_error
+ATLAS_DEGENERATE = 6
+ATLAS_MAX_SWEEPS = 64
+ATLAS_MAX_RESOLUTION = 16384
+ATLAS_MAX_GUTTER = 64
+ATLAS_BISECTION_STEPS = 24
+ATLAS_SIGNATURES = {
+    "gd_atlas_face_class": (_i, [_vp, _i, _i] + [_vp] * 3),                          # stream, V F, verts tri cls
+    "gd_atlas_hook": (_i, [_vp, _i, _i] + [_vp] * 6),                                # stream, F E, eh cls layer single parent
+                                                                                     # changed
+    "gd_atlas_jump": (_i, [_vp, _i, _vp]),                                           # stream, F, parent
+    "gd_atlas_roots": (_i, [_vp, _i] + [_vp] * 3),                                   # stream, F, cls parent is_root
+    "gd_atlas_bounds": (_i, [_vp] + [_i] * 3 + [_vp] * 9),                           # stream, V F C, verts tri cls parent scan
+                                                                                     # face_chart keys bounds count
+    "gd_atlas_emit": (_i, [_vp] + [_i] * 5 + [_f] + [_vp] * 8),                      # stream, V F C resolution gutter, scale,
+                                                             # verts tri cls face_chart bounds offsets corner_xy key
+    "gd_atlas_write_vt": (_i, [_vp] + [_i] * 3 + [_vp] * 4),                         # stream, n T resolution, row corner_xy vt ft
+    "gd_atlas_lost_faces": (_i, [_vp] + [_i] * 3 + [_vp] * 2 + [_i] + [_vp] * 3),    # stream, F H W, corner_xy rast, freeze,
+                                                                                     # lost layer single
+}
+
 # the second stage's neural shader and shading loss (include/gd_shader.h, which also fixes the layouts of the buffers);
 # messages go through gd_mesh_last_error
 _u32 = C.c_uint32
@@ -318,7 +340,8 @@ def lib():
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
                 + list(MESH_REMESH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
-                + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
+                + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()) \
+                + list(ATLAS_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args
@@ -331,7 +354,7 @@ def lib():
 _ERROR_CHANNELS = (("gd_scene_densify_stats", "gd_scene_last_error"), ("gd_scene_densify_", "gd_scene_densify_last_error"),
                    ("gd_scene_", "gd_scene_last_error"), ("gd_mesh_", "gd_mesh_last_error"),
                    ("gd_shader_", "gd_mesh_last_error"), ("gd_fit_", "gd_mesh_last_error"),
-                   ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
+                   ("gd_atlas_", "gd_mesh_last_error"), ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
                    ("gd_raster_", "gd_raster_last_error"))
 
 

@@ -4,7 +4,8 @@
 
   * ``grid_atlas(num_faces, resolution, gutter)``   an atlas that needs no unwrap: every triangle is its own right-triangle
                                                     chart, two per square cell (host, deterministic).  SEAM-HEAVY: every
-                                                    edge of the mesh is a seam; a chart-based unwrap is not built
+                                                    edge of the mesh is a seam; the chart-based unwrap is
+                                                    ``texture_atlas.chart_atlas`` (``atlas="chart"`` below)
   * ``uv_padding_index(mask, padding)``             per texel the covered texel it takes its colour from: the HIP kernel of
                                                     ``csrc/raster_bake.hip`` (definition: include/gd_bake.h) -- no CPU path
   * ``uv_padding(image, mask, padding)``            the padded 8-bit image (``gd_bake_resolve_u8`` after the index)
@@ -169,12 +170,18 @@ def write_textured_obj(path: str, v, f, vt, ft, albedo, reverse: bool = False) -
 
 
 def export_textured_mesh(save_path: str, field, v: torch.Tensor, f: torch.Tensor, texture_resolution: int = 2048,
-                         padding: int = 16, reverse: bool = False, vt=None, ft=None) -> List[str]:
+                         padding: int = 16, reverse: bool = False, vt=None, ft=None, atlas: str = "grid") -> List[str]:
     """``bake_texture`` + ``write_textured_obj``: the body of ``NeTFRenderer.export_mesh``.  Without ``vt`` / ``ft`` the
-    atlas is ``grid_atlas(F, texture_resolution)``."""
+    atlas is ``grid_atlas(F, texture_resolution)`` for ``atlas="grid"`` and ``texture_atlas.chart_atlas(v, f,
+    texture_resolution)`` for ``atlas="chart"``; UVs given by the caller win."""
     if (vt is None) != (ft is None):
         raise ValueError("export_mesh: give both vt and ft, or neither")
-    if vt is None:
+    if atlas not in ("grid", "chart"):
+        raise ValueError(f"export_mesh: atlas must be 'grid' or 'chart', not {atlas!r}")
+    if vt is None and atlas == "chart":
+        from .texture_atlas import chart_atlas
+        vt, ft, _ = chart_atlas(v, f, texture_resolution)
+    elif vt is None:
         vt, ft = grid_atlas(f.shape[0], texture_resolution)
     baked = bake_texture(field, v, f, vt, ft, texture_resolution, padding)
     return write_textured_obj(save_path, v, f, vt, ft, baked["albedo"], reverse=reverse)

@@ -415,10 +415,11 @@ class NeTFRenderer(MeshRenderer):
         from . import texture_fit
         return texture_fit.fit_texture(self, views, iters, resolution, hashgrid_lr, mlp_lr, seed, save_path, optimizer)
 
-    def export_mesh(self, save_path, texture_resolution=2048, padding=16, reverse=False, vt=None, ft=None):
+    def export_mesh(self, save_path, texture_resolution=2048, padding=16, reverse=False, vt=None, ft=None, atlas="grid"):
         """``Renderer.export_mesh`` (mesh_renderer.py:260-313) plus optional UVs: bakes ``texture_fn`` into the atlas ``vt`` /
-        ``ft`` (``texture_bake.grid_atlas`` of the mesh if not given: one chart per triangle, seam-heavy) and writes
-        ``save_path`` with its ``.mtl`` and ``_albedo.png``; returns the three paths.  Waits for the GPU (once per run)."""
+        ``ft`` (if not given: ``texture_bake.grid_atlas`` of the mesh for ``atlas="grid"``, one chart per triangle and
+        seam-heavy; ``texture_atlas.chart_atlas`` for ``atlas="chart"``) and writes ``save_path`` with its ``.mtl`` and
+        ``_albedo.png``; returns the three paths.  Waits for the GPU (once per run)."""
         from . import texture_bake
         return texture_bake.export_textured_mesh(save_path, self.texture_fn, self.v, self.f, texture_resolution, padding,
-                                                 reverse, vt, ft)
+                                                 reverse, vt, ft, atlas)
