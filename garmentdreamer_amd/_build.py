@@ -60,9 +60,10 @@ def _newer(target: str, deps) -> bool:
 
 
 def _headers():
+    """every csrc/*.h and include/*.h: an object is rebuilt when ANY header is newer, whether it includes it or not"""
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     inc = os.path.join(HERE, "..", "include")
-    hs += [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f.endswith(".h")]   # gd_raster.h, gd_nn.h, gd_scene.h
+    hs += [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f.endswith(".h")]
     return hs
 
 

@@ -39,17 +39,6 @@ int afail(const char* what, const char* msg)
     return mesh_fail(-1, buf);
 }
 
-int launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "atlas %s: %s", what, hipGetErrorString(e));
-        return mesh_fail(-2, buf);
-    }
-    return 0;
-}
-
 dim3 grid_of(int64_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); }
 
 __device__ __forceinline__ uint32_t order_key(float x)
@@ -349,7 +338,7 @@ int gd_atlas_face_class(void* stream, int V, int F, const float* verts, const in
     if (!verts || !tri || !cls) return afail(what, "null pointer");
     if (V < 1 || !faces_ok(F)) return afail(what, "V must be at least 1 and F in 1..2^29-1");
     hipLaunchKernelGGL(face_class_kernel, grid_of(F), dim3(kThreads), 0, (hipStream_t)stream, V, F, verts, tri, cls);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_hook(void* stream, int F, int E, const int32_t* eh, const int32_t* cls, const int32_t* layer,
@@ -360,7 +349,7 @@ int gd_atlas_hook(void* stream, int F, int E, const int32_t* eh, const int32_t* 
     if (!faces_ok(F) || E < 1 || (int64_t)E > 3 * (int64_t)F) return afail(what, "F must be in 1..2^29-1 and E in 1..3F");
     hipLaunchKernelGGL(hook_kernel, grid_of(E), dim3(kThreads), 0, (hipStream_t)stream, F, E, eh, cls, layer, single, parent,
                        changed);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_jump(void* stream, int F, int32_t* parent)
@@ -369,7 +358,7 @@ int gd_atlas_jump(void* stream, int F, int32_t* parent)
     if (!parent) return afail(what, "null pointer");
     if (!faces_ok(F)) return afail(what, "F must be in 1..2^29-1");
     hipLaunchKernelGGL(jump_kernel, grid_of(F), dim3(kThreads), 0, (hipStream_t)stream, F, parent);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_roots(void* stream, int F, const int32_t* cls, const int32_t* parent, int32_t* is_root)
@@ -378,7 +367,7 @@ int gd_atlas_roots(void* stream, int F, const int32_t* cls, const int32_t* paren
     if (!cls || !parent || !is_root) return afail(what, "null pointer");
     if (!faces_ok(F)) return afail(what, "F must be in 1..2^29-1");
     hipLaunchKernelGGL(roots_kernel, grid_of(F), dim3(kThreads), 0, (hipStream_t)stream, F, cls, parent, is_root);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_bounds(void* stream, int V, int F, int C, const float* verts, const int32_t* tri, const int32_t* cls,
@@ -394,7 +383,7 @@ int gd_atlas_bounds(void* stream, int V, int F, int C, const float* verts, const
     hipLaunchKernelGGL(bounds_kernel, grid_of(F), dim3(kThreads), 0, s, V, F, C, verts, tri, cls, parent, scan, face_chart, keys,
                        count);
     hipLaunchKernelGGL(bounds_decode_kernel, grid_of(4 * (int64_t)C), dim3(kThreads), 0, s, 4 * C, keys, bounds);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_emit(void* stream, int V, int F, int C, int resolution, int gutter, float scale, const float* verts,
@@ -409,7 +398,7 @@ int gd_atlas_emit(void* stream, int V, int F, int C, int resolution, int gutter,
     if (!(scale > 0.0f) || !isfinite(scale)) return afail(what, "scale must be positive and finite");
     hipLaunchKernelGGL(emit_kernel, grid_of(3 * (int64_t)F), dim3(kThreads), 0, (hipStream_t)stream, V, F, C, gutter, scale,
                        verts, tri, cls, face_chart, bounds, offsets, corner_xy, key);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_write_vt(void* stream, int n, int T, int resolution, const int64_t* row, const int32_t* corner_xy, float* vt,
@@ -421,7 +410,7 @@ int gd_atlas_write_vt(void* stream, int n, int T, int resolution, const int64_t*
     if (resolution < 1 || resolution > GD_ATLAS_MAX_RESOLUTION) return afail(what, "resolution must be in 1..16384");
     hipLaunchKernelGGL(write_vt_kernel, grid_of(n), dim3(kThreads), 0, (hipStream_t)stream, n, T, (float)(256 * resolution), row,
                        corner_xy, vt, ft);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 int gd_atlas_lost_faces(void* stream, int F, int H, int W, const int32_t* corner_xy, const float* rast, int freeze,
@@ -433,7 +422,7 @@ int gd_atlas_lost_faces(void* stream, int F, int H, int W, const int32_t* corner
     if (H < 1 || W < 1 || H > GD_ATLAS_MAX_RESOLUTION || W > GD_ATLAS_MAX_RESOLUTION) return afail(what, "H and W must be in 1..16384");
     hipLaunchKernelGGL(lost_faces_kernel, dim3((unsigned)((F + kLostWaves - 1) / kLostWaves)), dim3(kThreads), 0,
                        (hipStream_t)stream, F, H, W, corner_xy, rast, freeze, lost, layer, single);
-    return launched(what);
+    return mesh_launched("atlas", what);
 }
 
 }  // extern "C"

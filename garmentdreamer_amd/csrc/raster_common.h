@@ -138,5 +138,8 @@ void launch_render_backward(hipStream_t s, int V, int W, int H, int tiles_x, int
 
 int scene_fail(int code, const char* msg);   // records msg for gd_scene_last_error() and returns code (raster_scene.hip)
 int mesh_fail(int code, const char* msg);    // the same for gd_mesh_last_error() (raster_mesh.hip)
+// Tail of an entry point of that channel, after its launches: 0, or mesh_fail(-2, "<family> <what>: <HIP's error string>")
+// ("<what>: ..." when family is null or empty)
+int mesh_launched(const char* family, const char* what);
 
 }  // namespace gd

@@ -254,17 +254,6 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 size_t partials_of(size_t npix) { return (npix + GD_FIT_PIXELS_PER_PARTIAL - 1) / GD_FIT_PIXELS_PER_PARTIAL; }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-        return mesh_fail(-2, buf);
-    }
-    return 0;
-}
-
 // -1 with a message, or 0
 int validate(const char* what, int H, int W, bool all_present, bool all_aligned)
 {
@@ -312,7 +301,7 @@ int gd_fit_loss_forward(void* stream, int H, int W, int flip_rows, const float* 
                        p_aa, n_aa, center, rgb, tmask, bg, image, cosinesview, m, (float*)scratch);
     hipLaunchKernelGGL(fit_final_kernel, dim3(1), dim3(GD_FIT_FINAL_THREADS), 0, s, partials, (const float*)scratch,
                        (float*)stats);
-    return launched("fit loss forward");
+    return mesh_launched(nullptr, "fit loss forward");
 }
 
 int gd_fit_loss_backward(void* stream, int H, int W, int flip_rows, const float* c_aa, const float* a_aa, const float* rgb,
@@ -325,7 +314,7 @@ int gd_fit_loss_backward(void* stream, int H, int W, int flip_rows, const float*
     const size_t npix = (size_t)H * W;
     hipLaunchKernelGGL(fit_backward_kernel, dim3((unsigned)((npix + kBlockPixels - 1) / kBlockPixels)), dim3(kBlock), 0,
                        (hipStream_t)stream, npix, H, W, flip_rows, c_aa, a_aa, rgb, bg, m, (const float*)stats, dloss, dc_aa);
-    return launched("fit loss backward");
+    return mesh_launched(nullptr, "fit loss backward");
 }
 
 }  // extern "C"

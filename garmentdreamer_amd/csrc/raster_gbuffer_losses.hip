@@ -15,52 +15,14 @@
 #include <stdio.h>
 
 #include "../../include/gd_mesh_losses.h"
-#include "raster_common.h"
+#include "raster_mesh_common.h"
 
 namespace gd {
 namespace {
 
-constexpr float kNormEps = 1e-12f;    // torch.nn.functional.normalize
 constexpr float kErrEps = 1e-8f;      // cosine_similarity's default, the enhanced loss's error term
 constexpr float kViewEps = 1e-6f;     // the eps the reference passes for every cosine with the view direction
 constexpr int kSums = 6;              // e w, w, plain, hole (float); plain in, hole in (int32)
-
-struct V3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ V3 load3(const float* __restrict__ p, size_t i)
-{
-    return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
-}
-__device__ __forceinline__ void store3(float* __restrict__ p, size_t i, V3 v)
-{
-    p[3 * i] = v.x;
-    p[3 * i + 1] = v.y;
-    p[3 * i + 2] = v.z;
-}
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 scale(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 divide(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ float norm(V3 a) { return sqrtf(dot(a, a)); }
-
-struct Camera {
-    V3 row[3];
-    V3 center;
-};
-
-__device__ __forceinline__ Camera load_camera(const float* __restrict__ c)
-{
-    return Camera{{load3(c, 0), load3(c, 1), load3(c, 2)}, load3(c, 3)};
-}
-
-// n_cam = Rf (R n)
-__device__ __forceinline__ V3 to_camera(const Camera& c, V3 n)
-{
-    return V3{dot(c.row[0], n), -dot(c.row[1], n), -dot(c.row[2], n)};
-}
 
 // R^T h
 __device__ __forceinline__ V3 transposed(const Camera& c, V3 h)
@@ -72,20 +34,6 @@ __device__ __forceinline__ V3 transposed(const Camera& c, V3 h)
 
 // B(g) = R^T (g_0, -g_1, -g_2)
 __device__ __forceinline__ V3 to_world(const Camera& c, V3 g) { return transposed(c, V3{g.x, -g.y, -g.z}); }
-
-// d = -Rf (R u), u = (center - p) / max(l, 1e-12)
-__device__ __forceinline__ V3 view_direction(const Camera& c, V3 p, V3* u, float* l)
-{
-    const V3 v = sub(c.center, p);
-    *l = norm(v);
-    *u = divide(v, fmaxf(*l, kNormEps));
-    return V3{-dot(c.row[0], *u), dot(c.row[1], *u), dot(c.row[2], *u)};
-}
-
-__device__ __forceinline__ float cosine(V3 a, V3 b, float eps)
-{
-    return dot(a, b) / (fmaxf(norm(a), eps) * fmaxf(norm(b), eps));
-}
 
 // C_e(a, b): the adjoint of cos_e(a, b) towards b
 __device__ __forceinline__ V3 cosine_adjoint(V3 a, V3 b, float eps)
@@ -148,21 +96,6 @@ __device__ __forceinline__ Pixel pixel_terms(const Inputs& in, const Camera& cam
         px.in_hole = m > 0.0f && in.mask_rf[i] > 0.0f;
     }
     return px;
-}
-
-// the header's tree over the workgroup's 256 values; every thread receives the total
-template <typename T>
-__device__ __forceinline__ T block_tree_sum(T x, T* lds)
-{
-    const int t = threadIdx.x;
-    lds[t] = x;
-    __syncthreads();
-#pragma unroll
-    for (int stride = 128; stride > 0; stride >>= 1) {
-        if (t < stride) lds[t] += lds[t + stride];
-        __syncthreads();
-    }
-    return lds[0];
 }
 
 // partials: [kSums][blocks] words, rows 0..3 float, rows 4..5 int32
@@ -273,17 +206,6 @@ __global__ __launch_bounds__(256) void losses_backward_kernel(size_t npix, int t
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-int launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-        return mesh_fail(-2, buf);
-    }
-    return 0;
-}
-
 // -1 with a message, or 0: what both entries check before any device work
 int validate(const char* what, int H, int W, int terms, const Inputs& in, const float* camera)
 {
@@ -331,7 +253,7 @@ int gd_mesh_gbuffer_losses_forward(void* stream, int H, int W, int terms, const 
     hipLaunchKernelGGL(losses_pixel_kernel, dim3(blocks), dim3(256), 0, s, npix, terms, in, camera, epsilon,
                        (float*)scratch);
     hipLaunchKernelGGL(losses_final_kernel, dim3(1), dim3(256), 0, s, (int)blocks, (const float*)scratch, (float*)stats);
-    return launched("gbuffer losses forward");
+    return mesh_launched(nullptr, "gbuffer losses forward");
 }
 
 int gd_mesh_gbuffer_losses_backward(void* stream, int H, int W, int terms, const float* normal, const float* position,
@@ -347,7 +269,7 @@ int gd_mesh_gbuffer_losses_backward(void* stream, int H, int W, int terms, const
     const size_t npix = (size_t)H * W;
     hipLaunchKernelGGL(losses_backward_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        npix, terms, in, camera, epsilon, (const float*)stats, dloss, dnormal, dposition);
-    return launched("gbuffer losses backward");
+    return mesh_launched(nullptr, "gbuffer losses backward");
 }
 
 }  // extern "C"

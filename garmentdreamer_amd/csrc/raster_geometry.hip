@@ -15,41 +15,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/gd_mesh_geometry.h"
-#include "raster_common.h"
+#include "raster_mesh_common.h"
 
 namespace gd {
 namespace {
 
-constexpr float kNormEps = 1e-12f;   // torch.nn.functional.normalize
 constexpr float kCosEps = 1e-8f;     // torch.cosine_similarity
-
-struct V3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ V3 load3(const float* __restrict__ p, size_t i)
-{
-    return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
-}
-__device__ __forceinline__ void store3(float* __restrict__ p, size_t i, V3 v)
-{
-    p[3 * i] = v.x;
-    p[3 * i + 1] = v.y;
-    p[3 * i + 2] = v.z;
-}
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 scale(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 divide(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ float norm(V3 a) { return sqrtf(dot(a, a)); }
-__device__ __forceinline__ V3 cross(V3 u, V3 w)
-{
-    return V3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
 
 // adjoint of n = x / max(l, eps), l = |x|
 __device__ __forceinline__ V3 normalize_adjoint(V3 n, float l, V3 g)
@@ -154,20 +127,6 @@ __global__ __launch_bounds__(256) void corner_sum3_kernel(int V, int F, const in
 }
 
 // ---- the fixed-order sum -----------------------------------------------------------------------------------------------
-
-// the header's tree over the workgroup's 256 values; the total is returned to thread 0
-__device__ __forceinline__ float block_tree_sum(float x, float* lds)
-{
-    const int t = threadIdx.x;
-    lds[t] = x;
-    __syncthreads();
-#pragma unroll
-    for (int stride = 128; stride > 0; stride >>= 1) {
-        if (t < stride) lds[t] += lds[t + stride];
-        __syncthreads();
-    }
-    return lds[0];
-}
 
 // loss = (sum of n partials) / denom, or 0 if denom <= 0
 __global__ __launch_bounds__(256) void reduce_partials_kernel(int n, const float* __restrict__ partials, int denom,
@@ -284,19 +243,6 @@ __global__ __launch_bounds__(256) void consistency_backward_kernel(int F, int P,
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-int launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-        return mesh_fail(-2, buf);
-    }
-    return 0;
-}
-
-dim3 grid_of(int n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace
 }  // namespace gd
 
@@ -313,7 +259,7 @@ int gd_mesh_normals_forward(void* stream, int V, int F, const float* verts, cons
     hipStream_t s = (hipStream_t)stream;
     if (F > 0) hipLaunchKernelGGL(face_normals_kernel, grid_of(F), dim3(256), 0, s, V, F, verts, tri, fn);
     hipLaunchKernelGGL(vertex_normals_kernel, grid_of(V), dim3(256), 0, s, V, F, corner_ptr, corner_idx, fn, vn, len);
-    return launched("normals forward");
+    return mesh_launched(nullptr, "normals forward");
 }
 
 size_t gd_mesh_normals_backward_scratch_bytes(int F)
@@ -337,7 +283,7 @@ int gd_mesh_normals_backward(void* stream, int V, int F, const float* verts, con
                            (float4*)scratch);
     hipLaunchKernelGGL(corner_sum3_kernel, grid_of(V), dim3(256), 0, s, V, F, corner_ptr, corner_idx,
                        (const float4*)scratch, dverts);
-    return launched("normals backward");
+    return mesh_launched(nullptr, "normals backward");
 }
 
 size_t gd_mesh_loss_scratch_bytes(int n)
@@ -357,7 +303,7 @@ int gd_mesh_laplacian_forward(void* stream, int V, int N, const float* verts, co
     hipLaunchKernelGGL(laplacian_forward_kernel, grid_of(V), dim3(256), 0, s, V, N, verts, nbr_ptr, nbr_idx, delta,
                        (float*)scratch);
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, s, (V + 255) / 256, (const float*)scratch, V, loss);
-    return launched("laplacian forward");
+    return mesh_launched(nullptr, "laplacian forward");
 }
 
 int gd_mesh_laplacian_backward(void* stream, int V, int N, const int* nbr_ptr, const int* nbr_idx, const float* delta,
@@ -369,7 +315,7 @@ int gd_mesh_laplacian_backward(void* stream, int V, int N, const int* nbr_ptr, c
         return mesh_fail(-1, "laplacian backward: null pointer");
     hipLaunchKernelGGL(laplacian_backward_kernel, grid_of(V), dim3(256), 0, (hipStream_t)stream, V, N, nbr_ptr, nbr_idx,
                        delta, dloss, dverts);
-    return launched("laplacian backward");
+    return mesh_launched(nullptr, "laplacian backward");
 }
 
 int gd_mesh_normal_consistency_forward(void* stream, int F, int P, const float* fn, const int* face_nbr, float* loss,
@@ -382,7 +328,7 @@ int gd_mesh_normal_consistency_forward(void* stream, int F, int P, const float* 
     if (F > 0)
         hipLaunchKernelGGL(consistency_forward_kernel, grid_of(F), dim3(256), 0, s, F, fn, face_nbr, (float*)scratch);
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, s, (F + 255) / 256, (const float*)scratch, P, loss);
-    return launched("normal consistency forward");
+    return mesh_launched(nullptr, "normal consistency forward");
 }
 
 int gd_mesh_normal_consistency_backward(void* stream, int F, int P, const float* fn, const int* face_nbr,
@@ -394,7 +340,7 @@ int gd_mesh_normal_consistency_backward(void* stream, int F, int P, const float*
     if (!fn || !face_nbr || !dloss || !dfn) return mesh_fail(-1, "normal consistency backward: null pointer");
     hipLaunchKernelGGL(consistency_backward_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, F, P, fn, face_nbr,
                        dloss, dfn);
-    return launched("normal consistency backward");
+    return mesh_launched(nullptr, "normal consistency backward");
 }
 
 }  // extern "C"

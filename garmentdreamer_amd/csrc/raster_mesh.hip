@@ -667,20 +667,19 @@ const char* check_frame(int H, int W)
     return nullptr;
 }
 
-int launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-        return mfail(-2, buf);
-    }
-    return 0;
-}
-
 }  // namespace
 
 int mesh_fail(int code, const char* msg) { return mfail(code, msg); }
+
+int mesh_launched(const char* family, const char* what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    const bool plain = !family || !*family;
+    char buf[200];
+    snprintf(buf, sizeof(buf), "%s%s%s: %s", plain ? "" : family, plain ? "" : " ", what, hipGetErrorString(e));
+    return mfail(-2, buf);
+}
 
 }  // namespace gd
 
@@ -709,7 +708,7 @@ int gd_mesh_rasterize(void* stream, int V, int F, int H, int W, const float* pos
     }
     hipLaunchKernelGGL(raster_resolve_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, V, F, H, W, pos, tri, c.vis,
                        (float4*)rast);
-    return launched("rasterize");
+    return mesh_launched(nullptr, "rasterize");
 }
 
 int gd_mesh_interpolate_forward(void* stream, int V, int F, int C, int H, int W, const float* attr, const float* rast,
@@ -722,7 +721,7 @@ int gd_mesh_interpolate_forward(void* stream, int V, int F, int C, int H, int W,
     if (!rast || !out || (F > 0 && (!attr || !tri))) return mfail(-1, "interpolate: null pointer");
     hipLaunchKernelGGL(interp_forward_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, F, C, H * W,
                        attr, (const float4*)rast, tri, out);
-    return launched("interpolate forward");
+    return mesh_launched(nullptr, "interpolate forward");
 }
 
 size_t gd_mesh_interpolate_backward_scratch_bytes(int F, int C)
@@ -749,7 +748,7 @@ int gd_mesh_interpolate_backward(void* stream, int V, int F, int C, int H, int W
     const int64_t n = (int64_t)V * C;
     hipLaunchKernelGGL(vertex_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, V, F, C, corner_ptr,
                        corner_idx, (const float*)scratch, dattr);
-    return launched("interpolate backward");
+    return mesh_launched(nullptr, "interpolate backward");
 }
 
 int gd_mesh_antialias_weights(void* stream, int V, int F, int H, int W, const float* rast, const float* pos,
@@ -761,7 +760,7 @@ int gd_mesh_antialias_weights(void* stream, int V, int F, int H, int W, const fl
     if (!rast || !wts || (F > 0 && (!pos || !tri || !opp))) return mfail(-1, "antialias: null pointer");
     hipLaunchKernelGGL(aa_weights_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, F, H, W,
                        (const float4*)rast, pos, tri, opp, (float4*)wts);
-    return launched("antialias weights");
+    return mesh_launched(nullptr, "antialias weights");
 }
 
 int gd_mesh_antialias_apply(void* stream, int C, int H, int W, const float* in, const float* wts, float* out, int adjoint)
@@ -774,7 +773,7 @@ int gd_mesh_antialias_apply(void* stream, int C, int H, int W, const float* in, 
     const int64_t n = (int64_t)H * W * C;
     hipLaunchKernelGGL(aa_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, C, H, W, in,
                        (const float4*)wts, out, adjoint);
-    return launched("antialias apply");
+    return mesh_launched(nullptr, "antialias apply");
 }
 
 // ---- include/gd_mesh_deform.h ------------------------------------------------------------------------------------------
@@ -789,7 +788,7 @@ int gd_mesh_interpolate_backward_rast(void* stream, int V, int F, int C, int H, 
     if (!rast || !dout || !drast || (F > 0 && (!attr || !tri))) return mfail(-1, "interpolate: null pointer");
     hipLaunchKernelGGL(interp_backward_rast_kernel, dim3((H * W + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, F, C,
                        H * W, attr, (const float4*)rast, tri, dout, (float4*)drast);
-    return launched("interpolate backward (rast)");
+    return mesh_launched(nullptr, "interpolate backward (rast)");
 }
 
 size_t gd_mesh_rasterize_backward_scratch_bytes(int F)
@@ -815,7 +814,7 @@ int gd_mesh_rasterize_backward(void* stream, int V, int F, int H, int W, const f
     const int64_t n = (int64_t)V * 4;
     hipLaunchKernelGGL(vertex_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, V, F, 4, corner_ptr,
                        corner_idx, (const float*)scratch, dpos);
-    return launched("rasterize backward");
+    return mesh_launched(nullptr, "rasterize backward");
 }
 
 size_t gd_mesh_antialias_backward_pos_scratch_bytes(int F) { return gd_mesh_rasterize_backward_scratch_bytes(F); }
@@ -838,7 +837,7 @@ int gd_mesh_antialias_backward_pos(void* stream, int V, int F, int C, int H, int
     const int64_t n = (int64_t)V * 4;
     hipLaunchKernelGGL(vertex_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, V, F, 4, corner_ptr,
                        corner_idx, (const float*)scratch, dpos);
-    return launched("antialias backward (pos)");
+    return mesh_launched(nullptr, "antialias backward (pos)");
 }
 
 int gd_mesh_visible_vertices(void* stream, int V, int F, int npix, const float* rast, const int* tri, uint8_t* vis)
@@ -850,7 +849,7 @@ int gd_mesh_visible_vertices(void* stream, int V, int F, int npix, const float* 
     if (!rast || !tri || !vis) return mfail(-1, "visible vertices: null pointer");
     hipLaunchKernelGGL(visible_vertices_kernel, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t)stream, V, F, npix,
                        (const float4*)rast, tri, vis);
-    return launched("visible vertices");
+    return mesh_launched(nullptr, "visible vertices");
 }
 
 const char* gd_mesh_last_error(void) { return gd::g_mesh_err; }

@@ -7,51 +7,21 @@
 // kernel boundaries, nothing waits across workgroups.  No floating-point atomics.  The integer atomics are plain HIP
 // (atomicMin on 64-bit keys, atomicAdd / atomicOr on counters), device scope by default.  A kernel that writes through an
 // index it read from a table checks it against the capacity it was given and raises GD_REMESH_FLAG_CAPACITY instead.
+// The vector math, the connectivity tables (Conn), the two collapse tests shared with raster_simplify.hip and the ring
+// walks (spread_key, holds_key) are in raster_mesh_common.h.
 //
 // A remesh runs once or twice per deformation on tens of thousands of faces: nothing here is tuned.  The scan is ONE
 // workgroup that walks the array (no cross-workgroup carry to wait for); at 2*10^5 keys that is some 200 steps.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/gd_mesh_remesh.h"
-#include "raster_common.h"
+#include "raster_mesh_common.h"
 
 namespace gd {
 namespace {
 
-typedef unsigned long long u64;
 constexpr u64 kNoKey = ~(u64)0;
-constexpr float kNormEps = 1e-12f;
-
-struct V3 {
-    float x, y, z;
-};
-__device__ __forceinline__ V3 load3(const float* __restrict__ p, size_t i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__device__ __forceinline__ void store3(float* __restrict__ p, size_t i, V3 v)
-{
-    p[3 * i] = v.x;
-    p[3 * i + 1] = v.y;
-    p[3 * i + 2] = v.z;
-}
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 scale(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 u, V3 w)
-{
-    return V3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
-__device__ __forceinline__ float sqlen(V3 a, V3 b)
-{
-    const V3 d = sub(a, b);
-    return dot(d, d);
-}
-__device__ __forceinline__ V3 tri_normal(V3 p0, V3 p1, V3 p2) { return cross(sub(p1, p0), sub(p2, p0)); }
-__device__ __forceinline__ V3 midpoint(V3 a, V3 b) { return V3{0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z)}; }
-
-__device__ __forceinline__ bool in_range(int i, int n) { return (unsigned)i < (unsigned)n; }
 
 __device__ __forceinline__ int lower_bound(const int64_t* __restrict__ keys, int n, int64_t x)
 {
@@ -289,74 +259,20 @@ __global__ __launch_bounds__(256) void split_apply_kernel(int V, int F, int E, i
 
 // ---- collapse -----------------------------------------------------------------------------------------------------------
 
-struct Conn {
-    int V, F, E;
-    const float* verts;
-    const int *tri, *ev, *eh, *bnd, *nbr_ptr, *nbr_idx, *vf_ptr, *vf_idx;
-};
-
+// the remesher's rules: a boundary vertex moves only along the boundary, the link condition, no edge longer than hi
 __device__ bool collapse_allowed(const Conn& m, int a, int b, bool interior, float hi2)
 {
     if (m.bnd[a] && interior) return false;
     if (m.bnd[a] && m.bnd[b] && interior) return false;
-    const int a0 = m.nbr_ptr[a], a1 = m.nbr_ptr[a + 1], b0 = m.nbr_ptr[b], b1 = m.nbr_ptr[b + 1];
-    int common = 0;
-    for (int i = a0, j = b0; i < a1 && j < b1;) {
-        const int x = m.nbr_idx[i], y = m.nbr_idx[j];
-        if (x == y) {
-            common++;
-            i++;
-            j++;
-        } else if (x < y) i++;
-        else j++;
-    }
-    if (common != (interior ? 2 : 1)) return false;
+    int opposite[2];
+    if (common_neighbours(m, a, b, opposite) != (interior ? 2 : 1)) return false;
     const V3 pb = load3(m.verts, b);
-    for (int i = a0; i < a1; i++) {
+    for (int i = m.nbr_ptr[a]; i < m.nbr_ptr[a + 1]; i++) {
         const int n = m.nbr_idx[i];
         if (n == b || !in_range(n, m.V)) continue;
         if (sqlen(load3(m.verts, n), pb) > hi2) return false;
     }
-    for (int j = m.vf_ptr[a]; j < m.vf_ptr[a + 1]; j++) {
-        const int corner = m.vf_idx[j];
-        if (!in_range(corner, 3 * m.F)) return false;
-        const int f = corner / 3, i = corner - 3 * f;
-        const int x0 = m.tri[3 * (size_t)f], x1 = m.tri[3 * (size_t)f + 1], x2 = m.tri[3 * (size_t)f + 2];
-        if (x0 == b || x1 == b || x2 == b) continue;   // the face goes with the edge
-        if (!in_range(x0, m.V) || !in_range(x1, m.V) || !in_range(x2, m.V)) return false;
-        V3 p[3] = {load3(m.verts, x0), load3(m.verts, x1), load3(m.verts, x2)};
-        const V3 before = tri_normal(p[0], p[1], p[2]);
-        p[i] = pb;
-        if (!(dot(before, tri_normal(p[0], p[1], p[2])) > 0.0f)) return false;
-    }
-    return true;
-}
-
-// the minimum of key onto lo, hi and both their neighbourhoods
-__device__ __forceinline__ void spread_key(const Conn& m, int lo, int hi, u64 key, u64* __restrict__ vkey)
-{
-    atomicMin(&vkey[lo], key);
-    atomicMin(&vkey[hi], key);
-    for (int s = 0; s < 2; s++) {
-        const int v = s ? hi : lo;
-        for (int i = m.nbr_ptr[v]; i < m.nbr_ptr[v + 1]; i++) {
-            const int n = m.nbr_idx[i];
-            if (in_range(n, m.V)) atomicMin(&vkey[n], key);
-        }
-    }
-}
-
-__device__ __forceinline__ bool holds_key(const Conn& m, int lo, int hi, u64 key, const u64* __restrict__ vkey)
-{
-    if (vkey[lo] != key || vkey[hi] != key) return false;
-    for (int s = 0; s < 2; s++) {
-        const int v = s ? hi : lo;
-        for (int i = m.nbr_ptr[v]; i < m.nbr_ptr[v + 1]; i++) {
-            const int n = m.nbr_idx[i];
-            if (in_range(n, m.V) && vkey[n] != key) return false;
-        }
-    }
-    return true;
+    return collapse_keeps_normals<float>(m, a, b);
 }
 
 __global__ __launch_bounds__(256) void collapse_candidates_kernel(Conn m, float lo2, float hi2, int* __restrict__ dir,
@@ -713,33 +629,7 @@ __global__ __launch_bounds__(256) void edge_lengths_kernel(int V, int E, const f
     len[e] = (a >= 0 && a < V && b >= 0 && b < V) ? sqrtf(sqlen(load3(verts, a), load3(verts, b))) : 0.0f;
 }
 
-int launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "remesh %s: %s", what, hipGetErrorString(e));
-        return mesh_fail(-2, buf);
-    }
-    return 0;
-}
-
-dim3 grid_of(int n) { return dim3((unsigned)((max(n, 1) + 255) / 256)); }
-
-constexpr int kMaxFaces = 1 << 29;   // 3F and every corner index stay below 2^31
-
 bool sizes_ok(int V, int F, int E) { return V > 0 && F >= 0 && F < kMaxFaces && E >= 0 && E <= 3 * F; }
-
-Conn conn_of(const gd_remesh_mesh* m)
-{
-    return Conn{m->V, m->F, m->E, m->verts, m->tri, m->ev, m->eh, m->bnd, m->nbr_ptr, m->nbr_idx, m->vf_ptr, m->vf_idx};
-}
-
-bool mesh_ok(const gd_remesh_mesh* m)
-{
-    return m && sizes_ok(m->V, m->F, m->E) && m->verts && m->tri && m->ev && m->eh && m->bnd && m->nbr_ptr && m->nbr_idx &&
-           m->vf_ptr && m->vf_idx;
-}
 
 bool grid_ok(const gd_remesh_grid* g)
 {
@@ -764,21 +654,21 @@ int gd_mesh_remesh_scan(void* stream, int n, const int* in, int* out)
 {
     if (n < 0 || !out || (n > 0 && !in) || in == out) return mesh_fail(-1, "remesh scan: bad arguments");
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, in, out);
-    return launched("scan");
+    return mesh_launched("remesh", "scan");
 }
 
 int gd_mesh_remesh_keys(void* stream, int V, int F, const int* tri, int64_t* hkeys, int64_t* ckeys, int* flags)
 {
     if (!sizes_ok(V, F, 0) || F == 0 || !tri || !hkeys || !ckeys || !flags) return mesh_fail(-1, "remesh keys: bad arguments");
     hipLaunchKernelGGL(keys_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, V, F, tri, hkeys, ckeys, flags);
-    return launched("keys");
+    return mesh_launched("remesh", "keys");
 }
 
 int gd_mesh_remesh_heads(void* stream, int n, const int64_t* sorted_keys, int* head, int* flags)
 {
     if (n <= 0 || !sorted_keys || !head || !flags) return mesh_fail(-1, "remesh heads: bad arguments");
     hipLaunchKernelGGL(heads_kernel, grid_of(n), dim3(256), 0, (hipStream_t)stream, n, sorted_keys, head, flags);
-    return launched("heads");
+    return mesh_launched("remesh", "heads");
 }
 
 int gd_mesh_remesh_edge_tables(void* stream, int V, int F, int E, const int64_t* sorted_keys, const int64_t* order,
@@ -790,7 +680,7 @@ int gd_mesh_remesh_edge_tables(void* stream, int V, int F, int E, const int64_t*
         return mesh_fail(-1, "remesh edge tables: bad arguments");
     hipLaunchKernelGGL(edge_tables_kernel, grid_of(3 * F), dim3(256), 0, (hipStream_t)stream, V, 3 * F, E, sorted_keys, order,
                        head_scan, fe, ev, eh, ukeys, rkeys, bnd, flags);
-    return launched("edge tables");
+    return mesh_launched("remesh", "edge tables");
 }
 
 int gd_mesh_remesh_vertex_tables(void* stream, int V, int F, int E, const int64_t* ukeys, const int64_t* sorted_rkeys,
@@ -801,21 +691,21 @@ int gd_mesh_remesh_vertex_tables(void* stream, int V, int F, int E, const int64_
         return mesh_fail(-1, "remesh vertex tables: bad arguments");
     hipLaunchKernelGGL(vertex_tables_kernel, grid_of(V + 1), dim3(256), 0, (hipStream_t)stream, V, F, E, ukeys, sorted_rkeys,
                        sorted_ckeys, nbr_ptr, nbr_idx, vf_ptr, vf_idx);
-    return launched("vertex tables");
+    return mesh_launched("remesh", "vertex tables");
 }
 
 int gd_mesh_remesh_split_mark(void* stream, int V, int E, const float* verts, const int* ev, float hi2, int* mark)
 {
     if (V <= 0 || E <= 0 || !verts || !ev || !mark || !(hi2 > 0.0f)) return mesh_fail(-1, "remesh split mark: bad arguments");
     hipLaunchKernelGGL(split_mark_kernel, grid_of(E), dim3(256), 0, (hipStream_t)stream, V, E, verts, ev, hi2, mark);
-    return launched("split mark");
+    return mesh_launched("remesh", "split mark");
 }
 
 int gd_mesh_remesh_split_count(void* stream, int F, int E, const int* fe, const int* mark, int* count)
 {
     if (F <= 0 || E <= 0 || !fe || !mark || !count) return mesh_fail(-1, "remesh split count: bad arguments");
     hipLaunchKernelGGL(split_count_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, F, E, fe, mark, count);
-    return launched("split count");
+    return mesh_launched("remesh", "split count");
 }
 
 int gd_mesh_remesh_split_apply(void* stream, int V, int F, int E, int Vcap, int Fcap, const float* verts, const int* tri,
@@ -827,27 +717,27 @@ int gd_mesh_remesh_split_apply(void* stream, int V, int F, int E, int Vcap, int 
         return mesh_fail(-1, "remesh split apply: bad arguments");
     hipLaunchKernelGGL(split_apply_kernel, grid_of(max(E, F)), dim3(256), 0, (hipStream_t)stream, V, F, E, Vcap, Fcap, verts,
                        tri, ev, fe, mark, edge_scan, face_scan, verts_out, tri_out, flags);
-    return launched("split apply");
+    return mesh_launched("remesh", "split apply");
 }
 
 int gd_mesh_remesh_collapse_candidates(void* stream, const gd_remesh_mesh* mesh, float lo2, float hi2, int* dir,
                                        uint64_t* ekey, uint64_t* vkey)
 {
-    if (!mesh_ok(mesh) || mesh->E == 0 || !dir || !ekey || !vkey || !(lo2 > 0.0f) || !(hi2 > 0.0f))
+    if (!mesh_ok(mesh, false) || mesh->E == 0 || !dir || !ekey || !vkey || !(lo2 > 0.0f) || !(hi2 > 0.0f))
         return mesh_fail(-1, "remesh collapse candidates: bad arguments");
     hipLaunchKernelGGL(collapse_candidates_kernel, grid_of(mesh->E), dim3(256), 0, (hipStream_t)stream, conn_of(mesh), lo2,
                        hi2, dir, (u64*)ekey, (u64*)vkey);
-    return launched("collapse candidates");
+    return mesh_launched("remesh", "collapse candidates");
 }
 
 int gd_mesh_remesh_collapse_select(void* stream, const gd_remesh_mesh* mesh, const int* dir, const uint64_t* ekey,
                                    const uint64_t* vkey, int* remap, int* flags)
 {
-    if (!mesh_ok(mesh) || mesh->E == 0 || !dir || !ekey || !vkey || !remap || !flags)
+    if (!mesh_ok(mesh, false) || mesh->E == 0 || !dir || !ekey || !vkey || !remap || !flags)
         return mesh_fail(-1, "remesh collapse select: bad arguments");
     hipLaunchKernelGGL(collapse_select_kernel, grid_of(mesh->E), dim3(256), 0, (hipStream_t)stream, conn_of(mesh), dir,
                        (const u64*)ekey, (const u64*)vkey, remap, flags);
-    return launched("collapse select");
+    return mesh_launched("remesh", "collapse select");
 }
 
 int gd_mesh_remesh_relabel(void* stream, int V, int F, const int* tri, const int* remap, int* tri_out, int* alive, int* flags)
@@ -855,7 +745,7 @@ int gd_mesh_remesh_relabel(void* stream, int V, int F, const int* tri, const int
     if (!sizes_ok(V, F, 0) || F == 0 || !tri || !remap || !tri_out || !alive || !flags)
         return mesh_fail(-1, "remesh relabel: bad arguments");
     hipLaunchKernelGGL(relabel_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, V, F, tri, remap, tri_out, alive, flags);
-    return launched("relabel");
+    return mesh_launched("remesh", "relabel");
 }
 
 int gd_mesh_remesh_compact_faces(void* stream, int F, int Fcap, const int* tri, const int* alive, const int* alive_scan,
@@ -865,15 +755,15 @@ int gd_mesh_remesh_compact_faces(void* stream, int F, int Fcap, const int* tri, 
         return mesh_fail(-1, "remesh compact faces: bad arguments");
     hipLaunchKernelGGL(compact_faces_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, F, Fcap, tri, alive, alive_scan,
                        tri_out, flags);
-    return launched("compact faces");
+    return mesh_launched("remesh", "compact faces");
 }
 
 int gd_mesh_remesh_flip_candidates(void* stream, const gd_remesh_mesh* mesh, int* quad, uint64_t* ekey, uint64_t* vkey)
 {
-    if (!mesh_ok(mesh) || mesh->E == 0 || !quad || !ekey || !vkey) return mesh_fail(-1, "remesh flip candidates: bad arguments");
+    if (!mesh_ok(mesh, false) || mesh->E == 0 || !quad || !ekey || !vkey) return mesh_fail(-1, "remesh flip candidates: bad arguments");
     hipLaunchKernelGGL(flip_candidates_kernel, grid_of(mesh->E), dim3(256), 0, (hipStream_t)stream, conn_of(mesh), (int4*)quad,
                        (u64*)ekey, (u64*)vkey);
-    return launched("flip candidates");
+    return mesh_launched("remesh", "flip candidates");
 }
 
 int gd_mesh_remesh_flip_apply(void* stream, int V, int F, int E, const int* eh, const int* quad, const uint64_t* ekey,
@@ -883,15 +773,15 @@ int gd_mesh_remesh_flip_apply(void* stream, int V, int F, int E, const int* eh, 
         return mesh_fail(-1, "remesh flip apply: bad arguments");
     hipLaunchKernelGGL(flip_apply_kernel, grid_of(E), dim3(256), 0, (hipStream_t)stream, V, F, E, eh, (const int4*)quad,
                        (const u64*)ekey, (const u64*)vkey, tri, flags);
-    return launched("flip apply");
+    return mesh_launched("remesh", "flip apply");
 }
 
 int gd_mesh_remesh_relax(void* stream, const gd_remesh_mesh* mesh, float* verts_out, int* moved)
 {
-    if (!mesh_ok(mesh) || !verts_out || !moved || verts_out == mesh->verts)
+    if (!mesh_ok(mesh, false) || !verts_out || !moved || verts_out == mesh->verts)
         return mesh_fail(-1, "remesh relax: bad arguments");
     hipLaunchKernelGGL(relax_kernel, grid_of(mesh->V), dim3(256), 0, (hipStream_t)stream, conn_of(mesh), verts_out, moved);
-    return launched("relax");
+    return mesh_launched("remesh", "relax");
 }
 
 int gd_mesh_remesh_grid_bin(void* stream, const gd_remesh_grid* grid, int V, int F, const float* verts, const int* tri,
@@ -902,7 +792,7 @@ int gd_mesh_remesh_grid_bin(void* stream, const gd_remesh_grid* grid, int V, int
         return mesh_fail(-1, "remesh grid: bad arguments");
     hipLaunchKernelGGL(grid_bin_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, grid_of_c(grid), V, F, verts, tri,
                        scatter, count, start, items, capacity, flags);
-    return launched("grid");
+    return mesh_launched("remesh", "grid");
 }
 
 int gd_mesh_remesh_project(void* stream, const gd_remesh_grid* grid, int n, const float* points, const int* moved, int V,
@@ -914,14 +804,14 @@ int gd_mesh_remesh_project(void* stream, const gd_remesh_grid* grid, int n, cons
         return mesh_fail(-1, "remesh project: bad arguments");
     hipLaunchKernelGGL(project_kernel, grid_of(n), dim3(256), 0, (hipStream_t)stream, grid_of_c(grid), n, points, moved, V, F,
                        verts, tri, start, items, capacity, out, flags);
-    return launched("project");
+    return mesh_launched("remesh", "project");
 }
 
 int gd_mesh_remesh_used_vertices(void* stream, int V, int F, const int* tri, int* used, int* flags)
 {
     if (!sizes_ok(V, F, 0) || F == 0 || !tri || !used || !flags) return mesh_fail(-1, "remesh used vertices: bad arguments");
     hipLaunchKernelGGL(used_vertices_kernel, grid_of(F), dim3(256), 0, (hipStream_t)stream, V, F, tri, used, flags);
-    return launched("used vertices");
+    return mesh_launched("remesh", "used vertices");
 }
 
 int gd_mesh_remesh_compact_vertices(void* stream, int V, int F, int Vcap, const float* verts, const int* tri, const int* used,
@@ -931,14 +821,14 @@ int gd_mesh_remesh_compact_vertices(void* stream, int V, int F, int Vcap, const 
         return mesh_fail(-1, "remesh compact vertices: bad arguments");
     hipLaunchKernelGGL(compact_vertices_kernel, grid_of(max(V, F)), dim3(256), 0, (hipStream_t)stream, V, F, Vcap, verts, tri,
                        used, used_scan, verts_out, tri_out, flags);
-    return launched("compact vertices");
+    return mesh_launched("remesh", "compact vertices");
 }
 
 int gd_mesh_remesh_edge_lengths(void* stream, int V, int E, const float* verts, const int64_t* edges, float* len)
 {
     if (V <= 0 || E <= 0 || !verts || !edges || !len) return mesh_fail(-1, "remesh edge lengths: bad arguments");
     hipLaunchKernelGGL(edge_lengths_kernel, grid_of(E), dim3(256), 0, (hipStream_t)stream, V, E, verts, edges, len);
-    return launched("edge lengths");
+    return mesh_launched("remesh", "edge lengths");
 }
 
 }  // extern "C"

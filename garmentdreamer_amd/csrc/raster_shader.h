@@ -8,7 +8,6 @@ namespace gd {
 
 constexpr size_t kShaderSlabFloats = 256 * 256 + 256;   // Op_l Kp_l + Op_l of the largest layer
 
-int shader_launched(const char* what);                      // -2 with the text of a pending HIP error, or 0
 int shader_capacity_ok(const char* what, int64_t capacity); // -1 with a message unless 1 <= capacity <= 2^24
 int shader_null(const char* what);                          // -1, "null pointer"
 size_t shader_align256(size_t x);

@@ -14,46 +14,13 @@
 
 #include "../../include/gd_shader.h"
 #include "nn_device.h"
-#include "raster_common.h"
+#include "raster_mesh_common.h"
 #include "raster_shader.h"
 
 namespace gd {
 namespace {
 
-constexpr float kNormEps = 1e-12f;    // torch.nn.functional.normalize
 constexpr float kViewEps = 1e-6f;     // the eps the reference passes for every cosine with the view direction
-
-struct V3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ V3 load3(const float* __restrict__ p, size_t i)
-{
-    return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
-}
-__device__ __forceinline__ void store3(float* __restrict__ p, size_t i, V3 v)
-{
-    p[3 * i] = v.x;
-    p[3 * i + 1] = v.y;
-    p[3 * i + 2] = v.z;
-}
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 scale(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 divide(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ float norm(V3 a) { return sqrtf(dot(a, a)); }
-__device__ __forceinline__ float cosine(V3 a, V3 b, float eps)
-{
-    return dot(a, b) / (fmaxf(norm(a), eps) * fmaxf(norm(b), eps));
-}
-
-// u = (center - p) / max(l, 1e-12)
-__device__ __forceinline__ V3 unit_to_center(V3 center, V3 p, float* l)
-{
-    const V3 v = sub(center, p);
-    *l = norm(v);
-    return divide(v, fmaxf(*l, kNormEps));
-}
 
 struct Selection {
     const float *normal, *position, *mask, *view_mask, *camera;
@@ -65,12 +32,11 @@ struct Selection {
 __device__ __forceinline__ bool kept(const Selection& s, size_t i)
 {
     if (!(s.view_mask[i] > 0.0f && s.mask[i] > 0.0f)) return false;
-    const V3 row0 = load3(s.camera, 0), row1 = load3(s.camera, 1), row2 = load3(s.camera, 2), center = load3(s.camera, 3);
-    const V3 n = load3(s.normal, i);
-    const V3 n_cam = V3{dot(row0, n), -dot(row1, n), -dot(row2, n)};
+    const Camera cam = load_camera(s.camera);
+    const V3 n_cam = to_camera(cam, load3(s.normal, i));
+    V3 u;
     float l;
-    const V3 u = unit_to_center(center, load3(s.position, i), &l);
-    const V3 d = V3{-dot(row0, u), dot(row1, u), dot(row2, u)};
+    const V3 d = view_direction(cam, load3(s.position, i), &u, &l);
     if (!(cosine(d, n_cam, kViewEps) <= 0.0f)) return false;
     return s.all || gd_shader_hash32(s.seed, s.step, (uint32_t)i) < s.threshold;
 }
@@ -249,19 +215,6 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ par
 
 // ---- L1 ---------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ float block_tree_sum(float x, float* lds)
-{
-    const int t = threadIdx.x;
-    lds[t] = x;
-    __syncthreads();
-#pragma unroll
-    for (int stride = 128; stride > 0; stride >>= 1) {
-        if (t < stride) lds[t] += lds[t + stride];
-        __syncthreads();
-    }
-    return lds[0];
-}
-
 __device__ __forceinline__ float sigmoid(float logit) { return 1.0f / (1.0f + expf(-logit)); }
 
 __global__ __launch_bounds__(256) void l1_rows_kernel(const int32_t* __restrict__ index, const int32_t* __restrict__ counters,
@@ -373,17 +326,6 @@ int image_ok(const char* what, int H, int W)
 
 }  // namespace
 
-int shader_launched(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-        return mesh_fail(-2, buf);
-    }
-    return 0;
-}
-
 int shader_capacity_ok(const char* what, int64_t capacity)
 {
     if (capacity < 1 || capacity > ((int64_t)1 << 24)) {
@@ -441,7 +383,7 @@ int gd_shader_select(void* stream, int H, int W, const float* normal, const floa
     hipLaunchKernelGGL(select_count_kernel, dim3(blocks), dim3(256), 0, st, npix, s, counts);
     hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const int*)counts, offsets, capacity, counters);
     hipLaunchKernelGGL(select_scatter_kernel, dim3(blocks), dim3(256), 0, st, npix, s, (const int*)offsets, capacity, index);
-    return shader_launched("shader select");
+    return mesh_launched(nullptr, "shader select");
 }
 
 int gd_shader_features(void* stream, int H, int W, const float* position, const float* normal, const float* camera,
@@ -454,7 +396,7 @@ int gd_shader_features(void* stream, int H, int W, const float* position, const 
     uint16_t* a = (uint16_t*)act;
     hipLaunchKernelGGL(features_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, position,
                        normal, camera, index, counters, a + gd_shader_act_offset(0, rows), a + gd_shader_act_offset(5, rows));
-    return shader_launched("shader features");
+    return mesh_launched(nullptr, "shader features");
 }
 
 int gd_shader_features_points(void* stream, int64_t N, const float* position, const float* normal, const float* view_dir,
@@ -469,7 +411,7 @@ int gd_shader_features_points(void* stream, int64_t N, const float* position, co
     hipLaunchKernelGGL(features_points_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, N,
                        position, normal, view_dir, counters, a + gd_shader_act_offset(0, rows),
                        a + gd_shader_act_offset(5, rows));
-    return shader_launched("shader features of points");
+    return mesh_launched(nullptr, "shader features of points");
 }
 
 int gd_shader_pack(void* stream, const float* params, void* packed, void* packed_t)
@@ -478,7 +420,7 @@ int gd_shader_pack(void* stream, const float* params, void* packed, void* packed
     if (!params || !packed || !packed_t) return shader_null("shader pack");
     hipLaunchKernelGGL(pack_kernel, dim3(GD_SHADER_PACKED_ELEMS / 256), dim3(256), 0, (hipStream_t)stream, params,
                        (uint16_t*)packed, (uint16_t*)packed_t);
-    return shader_launched("shader pack");
+    return mesh_launched(nullptr, "shader pack");
 }
 
 int gd_shader_l1_forward(void* stream, int H, int W, int64_t capacity, const int32_t* index, const int32_t* counters,
@@ -492,7 +434,7 @@ int gd_shader_l1_forward(void* stream, int H, int W, int64_t capacity, const int
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(l1_rows_kernel, dim3(blocks), dim3(256), 0, st, index, counters, logits, rgb, (float*)scratch);
     hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(256), 0, st, (int)blocks, (const float*)scratch, counters, loss);
-    return shader_launched("shader L1");
+    return mesh_launched(nullptr, "shader L1");
 }
 
 int gd_shader_l1_backward(void* stream, int H, int W, int64_t capacity, const int32_t* index, const int32_t* counters,
@@ -504,7 +446,7 @@ int gd_shader_l1_backward(void* stream, int H, int W, int64_t capacity, const in
     const int64_t rows = gd_shader_rows(capacity);
     hipLaunchKernelGGL(l1_backward_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, index,
                        counters, logits, rgb, dloss, (uint16_t*)dz + gd_shader_dz_offset(7, rows), dlogits);
-    return shader_launched("shader L1 backward");
+    return mesh_launched(nullptr, "shader L1 backward");
 }
 
 int gd_shader_colour(void* stream, int64_t N, const float* logits, float* colour)
@@ -514,7 +456,7 @@ int gd_shader_colour(void* stream, int64_t N, const float* logits, float* colour
     if (!logits || !colour) return shader_null("shader colour");
     hipLaunchKernelGGL(colour_kernel, dim3((unsigned)((3 * N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, 3 * N, logits,
                        colour);
-    return shader_launched("shader colour");
+    return mesh_launched(nullptr, "shader colour");
 }
 
 int gd_shader_features_backward(void* stream, int H, int W, const float* position, const float* camera, int64_t capacity,
@@ -529,10 +471,10 @@ int gd_shader_features_backward(void* stream, int H, int W, const float* positio
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = (size_t)H * W * 3 * sizeof(float);
     if (hipMemsetAsync(dposition, 0, bytes, st) != hipSuccess || hipMemsetAsync(dnormal, 0, bytes, st) != hipSuccess)
-        return shader_launched("shader features backward");
+        return mesh_launched(nullptr, "shader features backward");
     hipLaunchKernelGGL(features_backward_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, rows, position, camera,
                        index, counters, dfeat, dextra, dposition, dnormal);
-    return shader_launched("shader features backward");
+    return mesh_launched(nullptr, "shader features backward");
 }
 
 }  // extern "C"

@@ -220,7 +220,7 @@ int gd_shader_forward_layer(void* stream, int l, int64_t capacity, const int32_t
                        (const uint16_t*)(a + gd_shader_act_offset(l, rows)),
                        (const uint16_t*)packed + gd_shader_packed_offset(l), params + gd_shader_param_offset(l, 1), L.O,
                        (const uint16_t*)nullptr, out, ldo, logits, (float*)nullptr);
-    return shader_launched("shader forward");
+    return mesh_launched(nullptr, "shader forward");
 }
 
 int gd_shader_backward_input_layer(void* stream, int l, int64_t capacity, const int32_t* counters, const void* packed_t,
@@ -241,7 +241,7 @@ int gd_shader_backward_input_layer(void* stream, int l, int64_t capacity, const 
                        (const uint16_t*)(d + gd_shader_dz_offset(l, rows)),
                        (const uint16_t*)packed_t + gd_shader_packed_offset(l), (const float*)nullptr, 0,
                        a + gd_shader_act_offset(l, rows), out, ldo, dfeat, dextra);
-    return shader_launched("shader input gradient");
+    return mesh_launched(nullptr, "shader input gradient");
 }
 
 int gd_shader_backward_weight_layer(void* stream, int l, int64_t capacity, const int32_t* counters, const void* act,
@@ -263,7 +263,7 @@ int gd_shader_backward_weight_layer(void* stream, int l, int64_t capacity, const
     hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((L.O * L.K + L.O + 255) / 256)), dim3(256), 0, st, L.O, L.K, L.Op, L.Kp,
                        slabs, S, counters, (const float*)partials, grad + gd_shader_param_offset(l, 0),
                        grad + gd_shader_param_offset(l, 1));
-    return shader_launched("shader weight gradient");
+    return mesh_launched(nullptr, "shader weight gradient");
 }
 
 }  // extern "C"

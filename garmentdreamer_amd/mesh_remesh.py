@@ -13,7 +13,8 @@ the read-back of counts that size the next buffer (a remesh happens once or twic
 a table from sorted keys, decides or moves anything is a kernel.  Host reads: one per connectivity build (the edge count and
 the input's error flags), two per split (new vertices and faces; the apply's flags), one or two per collapse round, one per
 flip round (what it applied), one per projection (the unprojected count), one or two per vertex compaction: about 30 in an
-iteration with full rounds."""
+iteration with full rounds.  The connectivity itself (``Connectivity``, ``build_connectivity``) lives in
+``mesh_connectivity``, with the atlas and the final-mesh post-process as its other users; both names are re-exported here."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,69 +25,11 @@ import torch
 
 from . import _native
 from ._launch import launch, require_gpu
+from .mesh_connectivity import (Connectivity, build_connectivity, drop_dead_faces, empty_i32, mesh_args, mesh_struct,
+                                new_flags, raise_flags, zeros_i32)
+from .mesh_connectivity import scan as _scan   # under the name it has always had here (the atlas tests take it from here)
 
 NAME = "mesh_remesh"
-_MAX_FACES = 1 << 29
-
-
-class Connectivity(NamedTuple):
-    """the tables of include/gd_mesh_remesh.h for one ``tri``, all int32 on the device"""
-    tri: torch.Tensor       # [F,3]
-    V: int
-    F: int
-    E: int
-    ev: torch.Tensor        # [E,2] (lo, hi), rows sorted
-    eh: torch.Tensor        # [E,2] half-edges 3 f + i, the second -1 on the boundary
-    fe: torch.Tensor        # [3F] edge of each half-edge
-    bnd: torch.Tensor       # [V]
-    nbr_ptr: torch.Tensor   # [V+1]
-    nbr_idx: torch.Tensor   # [2E]
-    vf_ptr: torch.Tensor    # [V+1]
-    vf_idx: torch.Tensor    # [3F]
-
-
-def _i32(n, dev):
-    return torch.empty(n, dtype=torch.int32, device=dev)
-
-
-def _zeros(n, dev):
-    return torch.zeros(n, dtype=torch.int32, device=dev)
-
-
-def _flags(dev):
-    return torch.zeros(_native.REMESH_FLAGS, dtype=torch.int32, device=dev)
-
-
-def _scan(x: torch.Tensor) -> torch.Tensor:
-    """int32 [n+1]: the exclusive scan of ``x`` and its total"""
-    out = _i32(x.shape[0] + 1, x.device)
-    launch("gd_mesh_remesh_scan", x.device, x.shape[0], x, out)
-    return out
-
-
-def _raise_flags(what: str, flags: List[int]) -> None:
-    if flags[_native.REMESH_FLAG_INDEX]:
-        raise ValueError(f"{NAME}.{what}: vertex index out of range")
-    if flags[_native.REMESH_FLAG_REPEATED]:
-        raise ValueError(f"{NAME}.{what}: a face lists a vertex twice")
-    if flags[_native.REMESH_FLAG_NONMANIFOLD]:
-        raise ValueError(f"{NAME}.{what}: an edge is shared by more than two triangles (non-manifold mesh)")
-    if flags[_native.REMESH_FLAG_CAPACITY]:
-        raise RuntimeError(f"{NAME}.{what}: a table entry or an output position was out of range; nothing was written there")
-
-
-def _mesh_args(what: str, vertices, indices) -> Tuple[torch.Tensor, torch.Tensor]:
-    v = require_gpu(f"{NAME}.{what}", "vertices", vertices, torch.float32, 3)
-    t = require_gpu(f"{NAME}.{what}", "indices", indices, None, 3)
-    if v.dim() != 2 or t.dim() != 2:
-        raise ValueError(f"{NAME}.{what}: vertices must be [V,3] and indices [F,3]")
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{NAME}.{what}: indices must be int32 or int64")
-    if v.shape[0] == 0 or t.shape[0] >= _MAX_FACES:
-        raise ValueError(f"{NAME}.{what}: needs at least one vertex and fewer than 2^29 faces")
-    if t.dtype == torch.int64 and t.numel() and int(torch.stack((t.min(), t.max())).abs().max()) >= 1 << 31:
-        raise ValueError(f"{NAME}.{what}: vertex index out of range")
-    return v.detach().contiguous(), t.detach().to(torch.int32).contiguous()
 
 
 def _target(what: str, h) -> float:
@@ -102,42 +45,9 @@ def _thresholds(h: float) -> Tuple[float, float]:
     return lo * lo, hi * hi
 
 
-def build_connectivity(tri: torch.Tensor, num_vertices: int, what: str = "build_connectivity") -> Connectivity:
-    """The connectivity of ``tri`` (int32 [F,3] on the GPU, F > 0).  ``ValueError`` for an index out of range, a face that
-    lists a vertex twice or an edge with more than two faces; nothing that follows an index has run by then."""
-    dev, V, F = tri.device, int(num_vertices), tri.shape[0]
-    flags = _flags(dev)
-    hkeys = torch.empty(3 * F, dtype=torch.int64, device=dev)
-    ckeys = torch.empty(3 * F, dtype=torch.int64, device=dev)
-    launch("gd_mesh_remesh_keys", dev, V, F, tri, hkeys, ckeys, flags)
-    skeys, order = torch.sort(hkeys, stable=True)
-    sckeys = torch.sort(ckeys).values
-    head = _i32(3 * F, dev)
-    launch("gd_mesh_remesh_heads", dev, 3 * F, skeys, head, flags)
-    head_scan = _scan(head)
-    got = torch.cat((head_scan[-1:], flags)).tolist()                  # the one host read of a build
-    E = got[0]
-    _raise_flags(what, got[1:])
-    fe, ev, eh = _i32(3 * F, dev), _i32(2 * E, dev), _i32(2 * E, dev)
-    ukeys = torch.empty(E, dtype=torch.int64, device=dev)
-    rkeys = torch.empty(E, dtype=torch.int64, device=dev)
-    bnd = _zeros(V, dev)
-    launch("gd_mesh_remesh_edge_tables", dev, V, F, E, skeys, order, head_scan, fe, ev, eh, ukeys, rkeys, bnd, flags)
-    srkeys = torch.sort(rkeys).values
-    nbr_ptr, nbr_idx, vf_ptr, vf_idx = _i32(V + 1, dev), _i32(2 * E, dev), _i32(V + 1, dev), _i32(3 * F, dev)
-    launch("gd_mesh_remesh_vertex_tables", dev, V, F, E, ukeys, srkeys, sckeys, nbr_ptr, nbr_idx, vf_ptr, vf_idx)
-    return Connectivity(tri, V, F, E, ev.view(E, 2), eh.view(E, 2), fe, bnd, nbr_ptr, nbr_idx, vf_ptr, vf_idx)
-
-
-def _mesh_struct(v: torch.Tensor, c: Connectivity):
-    m = _native.RemeshMesh(c.V, c.F, c.E, v.data_ptr(), c.tri.data_ptr(), c.ev.data_ptr(), c.eh.data_ptr(), c.bnd.data_ptr(),
-                           c.nbr_ptr.data_ptr(), c.nbr_idx.data_ptr(), c.vf_ptr.data_ptr(), c.vf_idx.data_ptr())
-    return C.byref(m)
-
-
 def _conn(what, v, t, conn: Optional[Connectivity]) -> Connectivity:
     if conn is None:
-        return build_connectivity(t, v.shape[0], what)
+        return build_connectivity(t, v.shape[0], f"{NAME}.{what}")
     if conn.V != v.shape[0] or conn.F != t.shape[0] or conn.tri.data_ptr() != t.data_ptr():
         raise ValueError(f"{NAME}.{what}: the connectivity does not belong to this mesh")
     return conn
@@ -147,88 +57,77 @@ def _conn(what, v, t, conn: Optional[Connectivity]) -> Connectivity:
 
 def split_long_edges(vertices, indices, h, conn: Optional[Connectivity] = None):
     """Split every edge longer than 4/3 h at its midpoint: ``(vertices [V+S,3], indices int32, S)``."""
-    v, t = _mesh_args("split_long_edges", vertices, indices)
+    v, t = mesh_args(f"{NAME}.split_long_edges", vertices, indices)
     h = _target("split_long_edges", h)
     if t.shape[0] == 0:
         return v, t, 0
     c = _conn("split_long_edges", v, t, conn)
     dev = v.device
-    mark, count = _i32(c.E, dev), _i32(c.F, dev)
+    mark, count = empty_i32(c.E, dev), empty_i32(c.F, dev)
     launch("gd_mesh_remesh_split_mark", dev, c.V, c.E, v, c.ev, _thresholds(h)[1], mark)
     launch("gd_mesh_remesh_split_count", dev, c.F, c.E, c.fe, mark, count)
     escan, fscan = _scan(mark), _scan(count)
     S, F2 = torch.stack((escan[-1], fscan[-1])).tolist()
     if S == 0:
         return v, t, 0
-    flags = _flags(dev)
+    flags = new_flags(dev)
     v2 = torch.empty((c.V + S, 3), dtype=torch.float32, device=dev)
     v2[:c.V] = v
     t2 = torch.empty((F2, 3), dtype=torch.int32, device=dev)
     launch("gd_mesh_remesh_split_apply", dev, c.V, c.F, c.E, c.V + S, F2, v, t, c.ev, c.fe, mark, escan, fscan, v2, t2, flags)
-    _raise_flags("split_long_edges", flags.tolist())
+    raise_flags(f"{NAME}.split_long_edges", flags.tolist())
     return v2, t2, S
 
 
 def collapse_short_edges_round(vertices, indices, h, conn: Optional[Connectivity] = None):
     """One round of collapses of edges shorter than 4/5 h: ``(indices int32 with the dead faces removed, collapsed)``.
     Vertices keep their indices (``compact_vertices`` drops the removed ones)."""
-    v, t = _mesh_args("collapse_short_edges_round", vertices, indices)
+    v, t = mesh_args(f"{NAME}.collapse_short_edges_round", vertices, indices)
     h = _target("collapse_short_edges_round", h)
     if t.shape[0] == 0:
         return t, 0
     c = _conn("collapse_short_edges_round", v, t, conn)
     dev = v.device
     lo2, hi2 = _thresholds(h)
-    m = _mesh_struct(v, c)
-    direction = _i32(c.E, dev)
+    m = mesh_struct(v, c)
+    direction = empty_i32(c.E, dev)
     ekey = torch.empty(c.E, dtype=torch.int64, device=dev)
     vkey = torch.full((c.V,), -1, dtype=torch.int64, device=dev)        # all ones: above every key
     remap = torch.arange(c.V, dtype=torch.int32, device=dev)
-    flags = _flags(dev)
+    flags = new_flags(dev)
     launch("gd_mesh_remesh_collapse_candidates", dev, m, lo2, hi2, direction, ekey, vkey)
     launch("gd_mesh_remesh_collapse_select", dev, m, direction, ekey, vkey, remap, flags)
-    relabelled, alive = torch.empty_like(t), _i32(c.F, dev)
-    launch("gd_mesh_remesh_relabel", dev, c.V, c.F, t, remap, relabelled, alive, flags)
-    alive_scan = _scan(alive)
-    got = torch.cat((alive_scan[-1:], flags)).tolist()
-    _raise_flags("collapse_short_edges_round", got[1:])
-    n = got[1 + _native.REMESH_FLAG_SELECTED]
-    if n == 0:
-        return t, 0
-    out = torch.empty((got[0], 3), dtype=torch.int32, device=dev)
-    launch("gd_mesh_remesh_compact_faces", dev, c.F, got[0], relabelled, alive, alive_scan, out, flags)
-    _raise_flags("collapse_short_edges_round", flags.tolist())
-    return out, n
+    return drop_dead_faces(f"{NAME}.collapse_short_edges_round", t, remap, flags)
 
 
 def flip_edges_round(vertices, indices, conn: Optional[Connectivity] = None):
     """One round of valence-improving edge flips: ``(indices int32, flipped)``."""
-    v, t = _mesh_args("flip_edges_round", vertices, indices)
+    v, t = mesh_args(f"{NAME}.flip_edges_round", vertices, indices)
     if t.shape[0] == 0:
         return t, 0
     c = _conn("flip_edges_round", v, t, conn)
     dev = v.device
-    quad = _i32(4 * c.E, dev)
+    quad = empty_i32(4 * c.E, dev)
     ekey = torch.empty(c.E, dtype=torch.int64, device=dev)
     vkey = torch.full((c.V,), -1, dtype=torch.int64, device=dev)
-    flags = _flags(dev)
+    flags = new_flags(dev)
     out = t.clone()
-    launch("gd_mesh_remesh_flip_candidates", dev, _mesh_struct(v, c), quad, ekey, vkey)
+    launch("gd_mesh_remesh_flip_candidates", dev, mesh_struct(v, c), quad, ekey, vkey)
     launch("gd_mesh_remesh_flip_apply", dev, c.V, c.F, c.E, c.eh, quad, ekey, vkey, out, flags)
     got = flags.tolist()
-    _raise_flags("flip_edges_round", got)
+    raise_flags(f"{NAME}.flip_edges_round", got)
     n = got[_native.REMESH_FLAG_SELECTED]
     return (out, n) if n else (t, 0)
 
 
 def tangential_relax(vertices, indices, conn: Optional[Connectivity] = None):
     """One Jacobi step of tangential smoothing: ``(vertices, moved int32 [V])``; boundary and isolated vertices stay."""
-    v, t = _mesh_args("tangential_relax", vertices, indices)
+    v, t = mesh_args(f"{NAME}.tangential_relax", vertices, indices)
     if t.shape[0] == 0:
-        return v, _zeros(v.shape[0], v.device)
+        return v, zeros_i32(v.shape[0], v.device)
     c = _conn("tangential_relax", v, t, conn)
-    out, moved = torch.empty_like(v), _i32(c.V, v.device)
-    launch("gd_mesh_remesh_relax", v.device, _mesh_struct(v, c), out, moved)
+    out, moved = torch.empty_like(v), empty_i32(c.V, v.device)
+    launch("gd_mesh_remesh_relax", v.device, mesh_struct(v, c), out, moved)
     return out, moved
 
 
@@ -246,11 +145,11 @@ def build_surface_grid(vertices, indices, min_cell: float = 0.0) -> SurfaceGrid:
     """Bin the triangles of a surface by bounding box into a uniform grid whose cell is at least its longest edge and
     ``min_cell``, doubled until the grid has at most 2^21 cells (the rule of the header).  Two host reads."""
     what = "build_surface_grid"
-    v, t = _mesh_args(what, vertices, indices)
+    v, t = mesh_args(f"{NAME}.{what}", vertices, indices)
     if t.shape[0] == 0:
         raise ValueError(f"{NAME}.{what}: the surface has no triangle")
     dev, V, F = v.device, v.shape[0], t.shape[0]
-    c = build_connectivity(t, V, what)
+    c = build_connectivity(t, V, f"{NAME}.{what}")
     lengths = torch.empty(c.E, dtype=torch.float32, device=dev)
     launch("gd_mesh_remesh_edge_lengths", dev, V, c.E, v, c.ev.to(torch.int64), lengths)
     box = torch.cat((v.amin(0), v.amax(0), lengths.max()[None])).tolist()
@@ -266,14 +165,14 @@ def build_surface_grid(vertices, indices, min_cell: float = 0.0) -> SurfaceGrid:
         cell *= 2.0
     grid = _native.RemeshGrid((C.c_float * 3)(*box[:3]), cell, (C.c_int32 * 3)(*dims))
     cells = dims[0] * dims[1] * dims[2]
-    flags, count = _flags(dev), _zeros(cells, dev)
+    flags, count = new_flags(dev), zeros_i32(cells, dev)
     capacity = 8 * F                                                    # a box no wider than a cell touches <= 2 per axis
-    items = _zeros(capacity, dev)
+    items = zeros_i32(capacity, dev)
     launch("gd_mesh_remesh_grid_bin", dev, C.byref(grid), V, F, v, t, 0, count, None, None, 0, flags)
     start = _scan(count)
     count.zero_()
     launch("gd_mesh_remesh_grid_bin", dev, C.byref(grid), V, F, v, t, 1, count, start, items, capacity, flags)
-    _raise_flags(what, flags.tolist())
+    raise_flags(f"{NAME}.{what}", flags.tolist())
     return SurfaceGrid(v, t, grid, cell, start, items)
 
 
@@ -291,7 +190,7 @@ def project_to_surface(vertices, surface: SurfaceGrid, moved: Optional[torch.Ten
     if v.shape[0] == 0:
         return v, 0
     dev = v.device
-    out, flags = torch.empty_like(v), _flags(dev)
+    out, flags = torch.empty_like(v), new_flags(dev)
     launch("gd_mesh_remesh_project", dev, C.byref(surface.grid), v.shape[0], v, moved, surface.vertices.shape[0],
            surface.indices.shape[0], surface.vertices, surface.indices, surface.start, surface.items,
            surface.items.shape[0], out, flags)
@@ -300,20 +199,20 @@ def project_to_surface(vertices, surface: SurfaceGrid, moved: Optional[torch.Ten
 
 def compact_vertices(vertices, indices):
     """Drop the vertices no face names, preserving order: ``(vertices, indices int32)``."""
-    v, t = _mesh_args("compact_vertices", vertices, indices)
+    v, t = mesh_args(f"{NAME}.compact_vertices", vertices, indices)
     dev, V, F = v.device, v.shape[0], t.shape[0]
     if F == 0:
         return v[:0], t
-    flags, used = _flags(dev), _zeros(V, dev)
+    flags, used = new_flags(dev), zeros_i32(V, dev)
     launch("gd_mesh_remesh_used_vertices", dev, V, F, t, used, flags)
     used_scan = _scan(used)
     got = torch.cat((used_scan[-1:], flags)).tolist()
-    _raise_flags("compact_vertices", got[1:])
+    raise_flags(f"{NAME}.compact_vertices", got[1:])
     if got[0] == V:
         return v, t
     v2, t2 = torch.empty((got[0], 3), dtype=torch.float32, device=dev), torch.empty_like(t)
     launch("gd_mesh_remesh_compact_vertices", dev, V, F, got[0], v, t, used, used_scan, v2, t2, flags)
-    _raise_flags("compact_vertices", flags.tolist())
+    raise_flags(f"{NAME}.compact_vertices", flags.tolist())
     return v2, t2
 
 
@@ -336,7 +235,7 @@ def remesh_botsch(vertices, indices, h, iterations: int = 10, project: bool = Tr
     ``ValueError`` for a bad ``h``, an index out of range, a non-manifold mesh or a face that lists a vertex twice.
     Vertices no face names are dropped."""
     what = "remesh_botsch"
-    v, t = _mesh_args(what, vertices, indices)
+    v, t = mesh_args(f"{NAME}.{what}", vertices, indices)
     h = _target(what, h)
     iterations, rounds = int(iterations), int(rounds)
     if iterations < 0 or rounds < 0:
@@ -344,7 +243,7 @@ def remesh_botsch(vertices, indices, h, iterations: int = 10, project: bool = Tr
     info: Dict[str, List[int]] = {"split": [], "collapsed": [], "flipped": [], "unprojected": []}
     if t.shape[0] == 0:
         return v[:0].clone(), t.clone(), info
-    conn = build_connectivity(t, v.shape[0], what)                      # the input's own errors, before anything moves
+    conn = build_connectivity(t, v.shape[0], f"{NAME}.{what}")          # the input's own errors, before anything moves
     v, t2 = compact_vertices(v, t)
     conn = conn if t2.data_ptr() == t.data_ptr() else None
     t = t2

@@ -11,7 +11,7 @@ kernels of ``csrc/raster_simplify.hip`` (C-ABI and definitions: include/gd_mesh_
   * ``write_obj(path, vertices, indices)``                                             plain ``v`` / ``f`` lines
 
 What is torch here is plumbing: allocation and fills, one ``torch.sort`` of the candidate keys per round, and the read-back
-of counts.  The connectivity, the compaction and the relabelling are the remesher's (``mesh_remesh``), unchanged.  Host reads
+of counts.  The connectivity, the relabelling and the compaction are those of ``mesh_connectivity``, unchanged.  Host reads
 per round: three (the connectivity build's edge count and flags; the faces left and the selected count; the compaction's
 flags).  Agreement with MeshLab is unverified."""
 from __future__ import annotations
@@ -22,80 +22,60 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
-from . import _native
-from . import mesh_remesh as mr
 from ._launch import launch
+from .mesh_connectivity import (Connectivity, build_connectivity, drop_dead_faces, mesh_args, mesh_struct, new_flags,
+                                zeros_i32)
+from .mesh_remesh import compact_vertices
 
 NAME = "mesh_simplify"
 
 
 def _mesh_args(what: str, vertices, indices) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``mesh_remesh._mesh_args`` under this module's name; a tensor that is not on the GPU is a ``ValueError`` here"""
+    """``mesh_connectivity.mesh_args``; a tensor that is not on the GPU is a ``ValueError`` here"""
     for t in (vertices, indices):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"{NAME}.{what}: the HIP kernels have no CPU path (vertices and indices must be on the GPU)")
-    try:
-        return mr._mesh_args(what, vertices, indices)
-    except (ValueError, TypeError) as e:
-        raise type(e)(str(e).replace(mr.NAME + ".", NAME + ".", 1)) from None
+    return mesh_args(f"{NAME}.{what}", vertices, indices)
 
 
-def _connectivity(what: str, t: torch.Tensor, V: int) -> mr.Connectivity:
-    try:
-        return mr.build_connectivity(t, V, what)
-    except ValueError as e:
-        raise ValueError(str(e).replace(mr.NAME + ".", NAME + ".", 1)) from None
-
-
-def vertex_quadrics(vertices: torch.Tensor, conn: mr.Connectivity) -> torch.Tensor:
+def vertex_quadrics(vertices: torch.Tensor, conn: Connectivity) -> torch.Tensor:
     """float64 [V,10]: the sum of the face quadrics of each vertex, in the order of its ``vf`` row"""
     q = torch.empty((conn.V, 10), dtype=torch.float64, device=vertices.device)
-    launch("gd_mesh_simplify_quadrics", vertices.device, mr._mesh_struct(vertices, conn), q)
+    launch("gd_mesh_simplify_quadrics", vertices.device, mesh_struct(vertices, conn), q)
     return q
 
 
-def collapse_candidates(vertices: torch.Tensor, conn: mr.Connectivity, quadrics: torch.Tensor):
+def collapse_candidates(vertices: torch.Tensor, conn: Connectivity, quadrics: torch.Tensor):
     """``(key int64 [E], direction int32 [E], cost float64 [E,2])`` of the header's candidate pass"""
     dev = vertices.device
     key = torch.empty(conn.E, dtype=torch.int64, device=dev)
     direction = torch.empty(conn.E, dtype=torch.int32, device=dev)
     cost = torch.empty((conn.E, 2), dtype=torch.float64, device=dev)
-    launch("gd_mesh_simplify_candidates", dev, mr._mesh_struct(vertices, conn), quadrics, key, direction, cost)
+    launch("gd_mesh_simplify_candidates", dev, mesh_struct(vertices, conn), quadrics, key, direction, cost)
     return key, direction, cost
 
 
 def decimation_round(vertices: torch.Tensor, indices: torch.Tensor, quadrics: torch.Tensor, target_faces: int, passes: int = 4,
-                     conn: mr.Connectivity = None):
+                     conn: Connectivity = None):
     """One round towards ``target_faces`` on one connectivity: ``(indices int32 with the dead faces removed, selected)``.
     ``vertices`` float32 [V,3] and ``indices`` int32 [F,3] contiguous on the GPU, F > ``target_faces``; ``quadrics`` is
     updated in place; vertices keep their indices."""
     what = "decimation_round"
     dev, V, F = vertices.device, vertices.shape[0], indices.shape[0]
-    c = conn if conn is not None else _connectivity(what, indices, V)
-    m = mr._mesh_struct(vertices, c)
+    c = conn if conn is not None else build_connectivity(indices, V, f"{NAME}.{what}")
+    m = mesh_struct(vertices, c)
     key, direction, _ = collapse_candidates(vertices, c, quadrics)
     budget = (F - int(target_faces) + 1) // 2
     threshold = torch.sort(key).values[min(budget, c.E) - 1:]          # a device pointer: no host read
-    lock = mr._zeros(V, dev)
+    lock = zeros_i32(V, dev)
     remap = torch.arange(V, dtype=torch.int32, device=dev)
     vkey = torch.empty(V, dtype=torch.int64, device=dev)
-    flags = mr._flags(dev)
+    flags = new_flags(dev)
     for _ in range(passes):
         vkey.fill_(-1)                                                  # all ones: above every key
         launch("gd_mesh_simplify_spread", dev, m, key, threshold, lock, vkey)
         launch("gd_mesh_simplify_select", dev, m, key, threshold, direction, vkey, remap, quadrics, lock, flags)
-    relabelled, alive = torch.empty_like(indices), mr._i32(F, dev)
-    launch("gd_mesh_remesh_relabel", dev, V, F, indices, remap, relabelled, alive, flags)
-    alive_scan = mr._scan(alive)
-    got = torch.cat((alive_scan[-1:], flags)).tolist()
-    mr._raise_flags(what, got[1:])
-    n = got[1 + _native.REMESH_FLAG_SELECTED]
-    if n == 0:
-        return indices, 0
-    out = torch.empty((got[0], 3), dtype=torch.int32, device=dev)
-    launch("gd_mesh_remesh_compact_faces", dev, F, got[0], relabelled, alive, alive_scan, out, flags)
-    mr._raise_flags(what, flags.tolist())
-    return out, n
+    return drop_dead_faces(f"{NAME}.{what}", indices, remap, flags)
 
 
 def decimate_quadric(vertices, indices, target_faces: int, passes: int = 4, max_rounds: int = 1024):
@@ -118,7 +98,7 @@ def decimate_quadric(vertices, indices, target_faces: int, passes: int = 4, max_
     info: Dict[str, object] = {"reached": True, "selected": [], "faces": []}
     if t.shape[0] == 0:
         return v.clone(), t.clone(), info
-    conn = _connectivity(what, t, v.shape[0])                          # the input's own errors, before anything is written
+    conn = build_connectivity(t, v.shape[0], f"{NAME}.{what}")          # the input's own errors, before anything is written
     if t.shape[0] <= target_faces:
         return v.clone(), t.clone(), info
     quadrics = vertex_quadrics(v, conn)
@@ -133,7 +113,7 @@ def decimate_quadric(vertices, indices, target_faces: int, passes: int = 4, max_
         if n == 0:
             info["reached"] = False
             break
-    v2, t2 = mr.compact_vertices(v, t)
+    v2, t2 = compact_vertices(v, t)
     # never the caller's own storage: a run that selected nothing on a mesh without unreferenced vertices changes nothing
     v2 = v2.clone() if v2.data_ptr() == vertices.data_ptr() else v2
     t2 = t2.clone() if t2.data_ptr() == indices.data_ptr() else t2
@@ -151,11 +131,11 @@ def taubin_smooth(vertices, indices, steps: int = 10, lam: float = 0.5, mu: floa
         raise ValueError(f"{NAME}.{what}: steps must be >= 0, lam and mu finite")
     if t.shape[0] == 0 or steps == 0:
         return v.clone()
-    conn = _connectivity(what, t, v.shape[0])
+    conn = build_connectivity(t, v.shape[0], f"{NAME}.{what}")
     a, b = v, torch.empty_like(v)
     for _ in range(steps):
         for w in (lam, mu):
-            launch("gd_mesh_simplify_smooth", v.device, mr._mesh_struct(a, conn), w, b)
+            launch("gd_mesh_simplify_smooth", v.device, mesh_struct(a, conn), w, b)
             a, b = b, (torch.empty_like(v) if a is v else a)
     return a
 
@@ -178,7 +158,7 @@ def post_process_mesh(vertices, indices, target_faces: int = 40000, smooth: bool
     ``(vertices float32, indices int32, info of decimate_quadric)``."""
     v, t = _mesh_args("post_process_mesh", vertices, indices)
     if t.shape[0]:
-        _connectivity("post_process_mesh", t, v.shape[0])              # the input's own errors, before anything is written
+        build_connectivity(t, v.shape[0], f"{NAME}.post_process_mesh")    # the input's own errors, before anything is written
     if rotate:
         v = rotate_upright(v)
     v, t, info = decimate_quadric(v, t, target_faces)

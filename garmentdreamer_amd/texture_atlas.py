@@ -24,14 +24,11 @@ import torch
 
 from . import _native
 from ._launch import launch
-from .mesh_remesh import Connectivity, _mesh_args, _scan, build_connectivity
+from .mesh_connectivity import Connectivity, build_connectivity, empty_i32, mesh_args, scan
 from .mesh_render import rasterize
 
 NAME = "texture_atlas"
-
-
-def _i32(n, dev):
-    return torch.empty(n, dtype=torch.int32, device=dev)
+_MESH = "mesh_remesh."   # the prefix the mesh checks' messages carry here: they were the remesher's own when this was written
 
 
 # ---- the packer: include/gd_atlas.h "PACKING", line for line ---------------------------------------------------------------
@@ -104,8 +101,8 @@ def pack_charts(bounds, resolution: int, gutter: int) -> Tuple[np.float32, np.nd
 
 def face_classes(vertices: torch.Tensor, indices: torch.Tensor) -> torch.Tensor:
     """int32 [F]: ``2 k + (n_k < 0)`` of the dominant axis ``k`` of each face's normal, 6 for a degenerate face."""
-    v, t = _mesh_args("face_classes", vertices, indices)
-    cls = _i32(t.shape[0], v.device)
+    v, t = mesh_args(_MESH + "face_classes", vertices, indices)
+    cls = empty_i32(t.shape[0], v.device)
     launch("gd_atlas_face_class", v.device, v.shape[0], t.shape[0], v, t, cls)
     return cls
 
@@ -131,16 +128,16 @@ def chart_labels(conn: Connectivity, cls: torch.Tensor, layer: Optional[torch.Te
 def chart_bounds(v: torch.Tensor, t: torch.Tensor, cls: torch.Tensor, labels: torch.Tensor):
     """``(C, face_chart int32 [F], bounds float32 [C,4], count int32 [C])``: charts numbered by ascending label"""
     dev, F = v.device, t.shape[0]
-    is_root = _i32(F, dev)
+    is_root = empty_i32(F, dev)
     launch("gd_atlas_roots", dev, F, cls, labels, is_root)
-    scan = _scan(is_root)
-    C = int(scan[-1])                                                   # the chart count sizes the tables
+    root_scan = scan(is_root)
+    C = int(root_scan[-1])                                                # the chart count sizes the tables
     if C == 0:
         raise ValueError(f"{NAME}: every face is degenerate")
-    face_chart, count = _i32(F, dev), _i32(C, dev)
+    face_chart, count = empty_i32(F, dev), empty_i32(C, dev)
     keys = torch.empty((C, 4), dtype=torch.int32, device=dev)
     bounds = torch.empty((C, 4), dtype=torch.float32, device=dev)
-    launch("gd_atlas_bounds", dev, v.shape[0], F, C, v, t, cls, labels, scan, face_chart, keys, bounds, count)
+    launch("gd_atlas_bounds", dev, v.shape[0], F, C, v, t, cls, labels, root_scan, face_chart, keys, bounds, count)
     return C, face_chart, bounds, count
 
 
@@ -177,7 +174,7 @@ def chart_atlas(vertices: torch.Tensor, indices: torch.Tensor, resolution: int =
     a chart of its own, and further rounds do only that until a round loses nothing.  ``trace``: a list that receives
     each round's tensors (tests).  ``ValueError`` for a non-manifold mesh and for a resolution too small for the charts'
     gutters."""
-    v, t = _mesh_args("chart_atlas", vertices, indices)
+    v, t = mesh_args(_MESH + "chart_atlas", vertices, indices)
     res, g, max_rounds = int(resolution), int(gutter), int(max_rounds)
     if not 1 <= res <= _native.ATLAS_MAX_RESOLUTION or not 0 <= g <= _native.ATLAS_MAX_GUTTER or max_rounds < 1:
         raise ValueError(f"chart_atlas: resolution must be in 1..{_native.ATLAS_MAX_RESOLUTION}, gutter in "
@@ -185,7 +182,7 @@ def chart_atlas(vertices: torch.Tensor, indices: torch.Tensor, resolution: int =
     if t.shape[0] == 0:
         raise ValueError("chart_atlas: the mesh has no faces")
     dev, F = v.device, t.shape[0]
-    conn = build_connectivity(t, v.shape[0], "chart_atlas")
+    conn = build_connectivity(t, v.shape[0], _MESH + "chart_atlas")
     cls = face_classes(v, t)
     layer = torch.zeros(F, dtype=torch.int32, device=dev)
     single = torch.zeros(F, dtype=torch.int32, device=dev)
@@ -197,7 +194,7 @@ def chart_atlas(vertices: torch.Tensor, indices: torch.Tensor, resolution: int =
         scale, offsets, sizes = pack_charts(bounds.cpu().numpy(), res, g)       # the one read of the bounds
         corner_xy, vt, ft = _emit(v, t, cls, face_chart, bounds, C, res, g, scale, offsets)
         rast = _rasterize_atlas(vt, ft, res)
-        lost = _i32(F, dev)
+        lost = empty_i32(F, dev)
         before = (layer.clone(), single.clone()) if trace is not None else None
         launch("gd_atlas_lost_faces", dev, F, res, res, corner_xy, rast, int(rnd >= max_rounds), lost, layer, single)
         n_lost = int(lost.sum())

@@ -188,9 +188,11 @@ def test_a_non_manifold_fan_is_refused_before_any_apply_kernel(monkeypatch):
     mr = _mr()
     v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1]], dtype=np.float32)
     tri = np.array([[0, 1, 2], [1, 0, 3], [0, 1, 4]], dtype=np.int32)                  # three faces on edge (0, 1)
+    from garmentdreamer_amd import mesh_connectivity as mc                             # the connectivity's launches are there
     launched = []
-    real = mr.launch
+    real, real_mc = mr.launch, mc.launch
     monkeypatch.setattr(mr, "launch", lambda name, *a: (launched.append(name), real(name, *a))[1])
+    monkeypatch.setattr(mc, "launch", lambda name, *a: (launched.append(name), real_mc(name, *a))[1])
     for call in (lambda: mr.remesh_botsch(_dev(v), _dev(tri), 0.5), lambda: mr.split_long_edges(_dev(v), _dev(tri), 0.5),
                  lambda: mr.collapse_short_edges_round(_dev(v), _dev(tri), 0.5), lambda: mr.flip_edges_round(_dev(v), _dev(tri))):
         with pytest.raises(ValueError, match="non-manifold"):

@@ -231,12 +231,13 @@ def test_deformer_final_mesh_leaves_the_deformer_unchanged(tmp_path):
 # ---- errors -------------------------------------------------------------------------------------------------------------------
 
 def test_bad_calls_raise_value_errors_before_anything_is_written(monkeypatch):
-    from garmentdreamer_amd import mesh_remesh as mr
+    from garmentdreamer_amd import mesh_connectivity as mc, mesh_remesh as mr
     ms = _ms()
     launched = []
-    real_ms, real_mr = ms.launch, mr.launch
+    real_ms, real_mr, real_mc = ms.launch, mr.launch, mc.launch
     monkeypatch.setattr(ms, "launch", lambda name, *a: (launched.append(name), real_ms(name, *a))[1])
     monkeypatch.setattr(mr, "launch", lambda name, *a: (launched.append(name), real_mr(name, *a))[1])
+    monkeypatch.setattr(mc, "launch", lambda name, *a: (launched.append(name), real_mc(name, *a))[1])
     v, tri = _gpu_mesh(*sr.mesh("quad"))
     fan_v = _dev(np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1]], dtype=np.float32))
     fan = _dev(np.array([[0, 1, 2], [1, 0, 3], [0, 1, 4]], dtype=np.int32))                 # three faces on edge (0, 1)

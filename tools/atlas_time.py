@@ -22,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from garmentdreamer_amd import texture_atlas as ta  # noqa: E402
 from garmentdreamer_amd import texture_bake as tb  # noqa: E402
-from garmentdreamer_amd.mesh_remesh import build_connectivity  # noqa: E402
+from garmentdreamer_amd.mesh_connectivity import build_connectivity  # noqa: E402
 
 
 def pleated_tube(nu, nv, r=0.3, h=1.0, depth=0.03, pleats=5):
