@@ -268,6 +268,37 @@ ATLAS_SIGNATURES = {
                                                                                      # lost layer single
 }
 
+# texture sampling for the textured render: rast_db, attribute derivatives, mip pyramid, the filter modes and the gradient
+# to the texture (include/gd_sample.h); messages go through gd_mesh_last_error
+SAMPLE_MAX_SIDE = 16384
+SAMPLE_MAX_LEVELS = 15
+SAMPLE_MAX_CHANNELS = 4
+SAMPLE_TEXEL = 4
+SAMPLE_FILTERS = {"nearest": 0, "linear": 1, "linear-mipmap-nearest": 2, "linear-mipmap-linear": 3}
+SAMPLE_BOUNDARIES = {"wrap": 0, "clamp": 1}
+
+
+class SamplePyramid(C.Structure):
+    """``gd_sample_pyramid``, passed by value"""
+    _fields_ = [("levels", C.c_int32), ("width", C.c_int32 * SAMPLE_MAX_LEVELS), ("height", C.c_int32 * SAMPLE_MAX_LEVELS),
+                ("offset", C.c_int32 * (SAMPLE_MAX_LEVELS + 1))]
+
+
+SAMPLE_SIGNATURES = {
+    "gd_sample_pyramid_layout": (_i, [_i] * 3 + [C.POINTER(SamplePyramid)]),         # Ht Wt max_mip_level, out
+    "gd_sample_taps": (_i, [_i]),
+    "gd_sample_rast_db": (_i, [_vp] + [_i] * 4 + [_vp] * 4),                         # stream, V F H W, rast pos tri rast_db
+    "gd_sample_interpolate_da": (_i, [_vp] + [_i] * 5 + [_vp] * 5),                  # stream, V F C H W, attr rast rast_db tri
+                                                                                     # out_da
+    "gd_sample_build_mips": (_i, [_vp, _i, _vp, SamplePyramid, _vp]),                # stream, C, tex, layout, pyr
+    "gd_sample_texture_forward": (_i, [_vp] + [_i] * 4 + [SamplePyramid] + [_vp] * 4),   # stream, N C filter boundary, layout,
+                                                                                     # pyr uv uv_da out
+    "gd_sample_texture_items": (_i, [_vp] + [_i] * 4 + [SamplePyramid] + [_vp] * 5), # ..., layout, uv uv_da dout keys vals
+    "gd_sample_texture_reduce": (_i, [_vp, C.c_int64, _i, SamplePyramid] + [_vp] * 4),   # stream, items C, layout, sorted_keys
+                                                                                     # order vals gpyr
+    "gd_sample_texture_fold": (_i, [_vp, _i, SamplePyramid, _vp, _vp]),              # stream, C, layout, gpyr dtex
+}
+
 # the second stage's neural shader and shading loss (include/gd_shader.h, which also fixes the layouts of the buffers);
 # messages go through gd_mesh_last_error
 _u32 = C.c_uint32
@@ -341,7 +372,7 @@ def lib():
                 + list(MESH_REMESH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()) \
-                + list(ATLAS_SIGNATURES.items()):
+                + list(ATLAS_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args
@@ -354,7 +385,8 @@ def lib():
 _ERROR_CHANNELS = (("gd_scene_densify_stats", "gd_scene_last_error"), ("gd_scene_densify_", "gd_scene_densify_last_error"),
                    ("gd_scene_", "gd_scene_last_error"), ("gd_mesh_", "gd_mesh_last_error"),
                    ("gd_shader_", "gd_mesh_last_error"), ("gd_fit_", "gd_mesh_last_error"),
-                   ("gd_atlas_", "gd_mesh_last_error"), ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
+                   ("gd_atlas_", "gd_mesh_last_error"), ("gd_sample_", "gd_mesh_last_error"),
+                   ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
                    ("gd_raster_", "gd_raster_last_error"))
 
 

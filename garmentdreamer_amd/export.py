@@ -89,6 +89,79 @@ def save_image_rgb(path: str, rgb8) -> str:
     return path
 
 
+def load_image_rgb(path: str) -> np.ndarray:
+    """uint8 [H,W,3] or [H,W,4] of an 8-bit PNG of colour type 2 (RGB) or 6 (RGBA), not interlaced, row filters 0-4: what
+    ``save_image_rgb`` / ``save_image_rgba`` write and what other writers make of the same pixels.  Anything else (another
+    bit depth or colour type, interlacing, a broken file) raises ``ValueError`` naming it.  ``zlib`` and ``struct`` only."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file (signature)")
+    at, header, idat, ended = 8, None, [], False
+    while at + 8 <= len(data) and not ended:
+        (length,), tag = struct.unpack(">I", data[at:at + 4]), data[at + 4:at + 8]
+        body = data[at + 8:at + 8 + length]
+        if len(body) != length or at + 12 + length > len(data):
+            raise ValueError(f"{path}: truncated {tag!r} chunk")
+        if struct.unpack(">I", data[at + 8 + length:at + 12 + length])[0] != (zlib.crc32(tag + body) & 0xFFFFFFFF):
+            raise ValueError(f"{path}: CRC mismatch in the {tag!r} chunk")
+        if tag == b"IHDR":
+            header = struct.unpack(">IIBBBBB", body)
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            ended = True
+        at += 12 + length
+    if header is None or not idat or not ended:
+        raise ValueError(f"{path}: missing IHDR, IDAT or IEND chunk")
+    W, H, depth, colour, compression, filtering, interlace = header
+    if depth != 8:
+        raise ValueError(f"{path}: bit depth {depth} is not supported (8 only)")
+    if colour not in (2, 6):
+        raise ValueError(f"{path}: colour type {colour} is not supported (2 = RGB and 6 = RGBA only)")
+    if interlace != 0:
+        raise ValueError(f"{path}: interlaced (Adam7) images are not supported")
+    if compression != 0 or filtering != 0 or W < 1 or H < 1:
+        raise ValueError(f"{path}: unknown compression or filter method, or an empty image")
+    bpp = 3 if colour == 2 else 4
+    stride = W * bpp
+    raw = zlib.decompress(b"".join(idat))
+    if len(raw) != H * (stride + 1):
+        raise ValueError(f"{path}: {len(raw)} bytes of pixel data, expected {H * (stride + 1)}")
+    rows = np.frombuffer(raw, dtype=np.uint8).reshape(H, stride + 1)
+    out = np.zeros((H, stride), dtype=np.uint8)
+    prior = np.zeros(stride, dtype=np.int64)
+    for r in range(H):
+        kind, line = int(rows[r, 0]), rows[r, 1:].astype(np.int64)
+        if kind == 0:
+            cur = line
+        elif kind == 2:                                            # Up
+            cur = (line + prior) & 255
+        elif kind == 1:                                            # Sub: a running sum per channel
+            cur = (np.cumsum(line.reshape(W, bpp), axis=0) & 255).reshape(stride)
+        elif kind in (3, 4):                                       # Average, Paeth: each byte needs its left neighbour
+            cur = np.zeros(stride, dtype=np.int64)
+            src, up = line.tolist(), prior.tolist()
+            res = [0] * stride
+            for i in range(stride):
+                a = res[i - bpp] if i >= bpp else 0
+                b = up[i]
+                if kind == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = up[i - bpp] if i >= bpp else 0
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
+                res[i] = (src[i] + pred) & 255
+            cur[:] = res
+        else:
+            raise ValueError(f"{path}: row filter type {kind} is not defined")
+        out[r] = cur
+        prior = cur
+    return out.reshape(H, W, bpp)
+
+
 def dump_test_view(save_dir: str, out: Dict, batch: Dict, camera_info_list: List[Dict], alpha_threshold: float = 0.5,
                    view: int = 0):
     """``test_step`` (GaussianDreamer.py:334-410) for one rendered view: thresholded alpha as the mask, RGBA PNG
