@@ -195,6 +195,45 @@ MESH_SIMPLIFY_SIGNATURES = {
     "gd_mesh_simplify_rotate": (_i, [_vp, _i, _vp, _vp]),                          # stream, V, verts verts_out
 }
 
+# mesh cleaning: weld, null and duplicate faces, small components, non-manifold edges and vertices
+# (include/gd_mesh_clean.h); it shares the grid struct and the scan of the remesher
+CLEAN_STATS = 16
+CLEAN_STAT_INDEX, CLEAN_STAT_NONFINITE, CLEAN_STAT_REFERENCED, CLEAN_STAT_MERGED, CLEAN_STAT_NULL = 0, 1, 2, 3, 4
+CLEAN_STAT_DUPLICATE, CLEAN_STAT_COMPONENTS, CLEAN_STAT_COMPONENTS_REMOVED, CLEAN_STAT_COMPONENT_FACES = 5, 6, 7, 8
+CLEAN_STAT_SPLIT = 9
+CLEAN_MAX_ROUNDS = 16
+CLEAN_MAX_CELLS = 1 << 21
+MESH_CLEAN_SIGNATURES = {
+    "gd_mesh_clean_check": (_i, [_vp, _i, _i] + [_vp] * 6),                        # stream, V F, verts tri used box box_keys stats
+    "gd_mesh_clean_grid_bin": (_i, [_vp, _RG, _i, _vp, _vp, _i, _vp, _vp, _vp]),   # stream, grid, V, verts used, scatter, count
+                                                                                   # start items
+    "gd_mesh_clean_merge_rounds": (_i, [_vp, _RG, _i] + [_vp] * 4 + [_f, _i] + [_vp] * 3),   # stream, grid, V, verts used start
+                                                                                   # items, r2 rounds, state_a state_b undecided
+    "gd_mesh_clean_merge_target": (_i, [_vp, _RG, _i] + [_vp] * 4 + [_f, _i] + [_vp] * 3),   # ..., r2 merge, state target stats
+    "gd_mesh_clean_relabel": (_i, [_vp, _i, _i] + [_vp] * 7),                      # stream, V F, verts tri target tri_out alive
+                                                                                   # akey stats
+    "gd_mesh_clean_edge_keys": (_i, [_vp, _i, _i] + [_vp] * 3),                    # stream, V F, tri alive hkeys
+    "gd_mesh_clean_edge_table": (_i, [_vp, _i] + [_vp] * 4),                       # stream, n, skeys order she pos
+    "gd_mesh_clean_duplicates": (_i, [_vp, _i] + [_vp] * 7),                       # stream, F, tri alive_in skeys she pos
+                                                                                   # alive_out stats
+    "gd_mesh_clean_face_sweeps": (_i, [_vp, _i] + [_vp] * 3 + [_i, _i] + [_vp] * 2),   # stream, F, skeys she alive, sweeps init,
+                                                                                   # parent changed
+    "gd_mesh_clean_component_stats": (_i, [_vp, _i, _i] + [_vp] * 6),              # stream, V F, verts tri alive parent ckeys
+                                                                                   # ccount
+    "gd_mesh_clean_component_filter": (_i, [_vp, _i] + [_vp] * 4 + [_i, _f] + [_vp] * 3),   # stream, F, alive_in parent ckeys
+                                                                                   # ccount, min_faces t2, label alive_out stats
+    "gd_mesh_clean_edge_rounds": (_i, [_vp, _i] + [_vp] * 3 + [_i] + [_vp] * 3),   # stream, F, skeys she akey, rounds, live_a
+                                                                                   # live_b over
+    "gd_mesh_clean_corner_sweeps": (_i, [_vp, _i] + [_vp] * 4 + [_i, _i] + [_vp] * 2),   # stream, F, tri skeys she alive,
+                                                                                   # sweeps init, parent changed
+    "gd_mesh_clean_fan_roots": (_i, [_vp, _i, _i] + [_vp] * 7),                    # stream, V F, tri alive parent vmin used
+                                                                                   # split_key stats
+    "gd_mesh_clean_fan_ranks": (_i, [_vp, _i, _i, _vp, _vp]),                      # stream, n S, sorted_keys crank
+    "gd_mesh_clean_compact_faces": (_i, [_vp, _i, _i] + [_vp] * 5),                # stream, F Fout, tri alive fscan tri_out face_map
+    "gd_mesh_clean_emit": (_i, [_vp] + [_i] * 5 + [_vp] * 14),                     # stream, V F Fout V0 S, verts tri alive fscan
+                                           # used vscan target parent crank sorted_keys verts_out tri_out face_map vertex_map
+}
+
 # the second stage's G-buffer losses: enhanced / plain normal map and hole mask, one view per call (include/gd_mesh_losses.h)
 MESH_LOSS_ENHANCED, MESH_LOSS_PLAIN, MESH_LOSS_HOLE = 1, 2, 4
 MESH_LOSS_STATS_WORDS = 6
@@ -372,7 +411,7 @@ def lib():
                 + list(MESH_REMESH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()) \
-                + list(ATLAS_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()):
+                + list(ATLAS_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args

@@ -21,13 +21,12 @@
 #include <stdio.h>
 
 #include "../../include/gd_atlas.h"
-#include "raster_common.h"
+#include "raster_mesh_common.h"
 
 namespace gd {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxFaces = 1 << 29;   // 3F and every corner index stay below 2^31
 constexpr int kSlots = 64;
 constexpr int kProbes = 3;
 constexpr uint32_t kKeyMax = 0xFFFFFFFFu;
@@ -37,19 +36,6 @@ int afail(const char* what, const char* msg)
     char buf[200];
     snprintf(buf, sizeof(buf), "atlas %s: %s", what, msg);
     return mesh_fail(-1, buf);
-}
-
-dim3 grid_of(int64_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); }
-
-__device__ __forceinline__ uint32_t order_key(float x)
-{
-    const uint32_t u = __float_as_uint(x);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-
-__device__ __forceinline__ float order_value(uint32_t k)
-{
-    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
 
 // the corner's (a, b) of the header for a class 0..5
@@ -83,17 +69,6 @@ __global__ __launch_bounds__(kThreads) void face_class_kernel(int V, int F, cons
         }
     }
     cls[f] = out;
-}
-
-__device__ __forceinline__ int root_of(const int32_t* parent, int x, int F)
-{
-    // relaxed device-scope loads: other workgroups lower parent while this walk runs
-    int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != x && p >= 0 && p < F) {
-        x = p;
-        p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return x;
 }
 
 __global__ __launch_bounds__(kThreads) void hook_kernel(int F, int E, const int32_t* __restrict__ eh,
@@ -382,7 +357,7 @@ int gd_atlas_bounds(void* stream, int V, int F, int C, const float* verts, const
     hipLaunchKernelGGL(bounds_init_kernel, grid_of(C), dim3(kThreads), 0, s, C, keys, count);
     hipLaunchKernelGGL(bounds_kernel, grid_of(F), dim3(kThreads), 0, s, V, F, C, verts, tri, cls, parent, scan, face_chart, keys,
                        count);
-    hipLaunchKernelGGL(bounds_decode_kernel, grid_of(4 * (int64_t)C), dim3(kThreads), 0, s, 4 * C, keys, bounds);
+    hipLaunchKernelGGL(bounds_decode_kernel, grid_of(4 * C), dim3(kThreads), 0, s, 4 * C, keys, bounds);
     return mesh_launched("atlas", what);
 }
 
@@ -396,7 +371,7 @@ int gd_atlas_emit(void* stream, int V, int F, int C, int resolution, int gutter,
     if (resolution < 1 || resolution > GD_ATLAS_MAX_RESOLUTION) return afail(what, "resolution must be in 1..16384");
     if (gutter < 0 || gutter > GD_ATLAS_MAX_GUTTER) return afail(what, "gutter must be in 0..64");
     if (!(scale > 0.0f) || !isfinite(scale)) return afail(what, "scale must be positive and finite");
-    hipLaunchKernelGGL(emit_kernel, grid_of(3 * (int64_t)F), dim3(kThreads), 0, (hipStream_t)stream, V, F, C, gutter, scale,
+    hipLaunchKernelGGL(emit_kernel, grid_of(3 * F), dim3(kThreads), 0, (hipStream_t)stream, V, F, C, gutter, scale,
                        verts, tri, cls, face_chart, bounds, offsets, corner_xy, key);
     return mesh_launched("atlas", what);
 }

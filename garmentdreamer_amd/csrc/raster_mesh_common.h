@@ -1,6 +1,7 @@
 // raster_mesh_common.h -- device and host primitives shared by the mesh translation units of libgd_raster.so
-// (raster_geometry, raster_remesh, raster_simplify, raster_shader, raster_gbuffer_losses): the three-component vector math,
-// the range check, the fixed LDS tree sum, the connectivity tables of include/gd_mesh_remesh.h with the collapse tests and
+// (raster_geometry, raster_remesh, raster_simplify, raster_atlas, raster_clean, raster_shader, raster_gbuffer_losses): the
+// three-component vector math, the range check, the order keys of exact bounds, the root walk of the hooking forests, the
+// fixed LDS tree sum, the connectivity tables of include/gd_mesh_remesh.h with the collapse tests and
 // ring walks that stand on them, and the camera terms of the two shading files.  Internal to garmentdreamer_amd/csrc.
 // One definition each: these files are built with -ffp-contract=off and compared bit for bit with numpy statements, and
 // the ORDER of every operation below (the parentheses of dot, the strides of block_tree_sum) is fixed by
@@ -75,6 +76,31 @@ __device__ __forceinline__ Vec3<T> midpoint(Vec3<T> a, Vec3<T> b)
 
 // ---- range check and the fixed-order sum ----------------------------------------------------------------------------
 __device__ __forceinline__ bool in_range(int i, int n) { return (unsigned)i < (unsigned)n; }
+
+// The order-preserving integer key of a float (include/gd_atlas.h section 3): finite floats compare as the reals do, -0 below
+// +0, so an exact minimum or maximum can be taken by integer atomics; order_value is its inverse.
+__device__ __forceinline__ uint32_t order_key(float x)
+{
+    const uint32_t u = __float_as_uint(x);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+__device__ __forceinline__ float order_value(uint32_t k)
+{
+    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+
+// The root of x in a hooking forest with parent[y] <= y (include/gd_atlas.h section 2), so the walk ends.  Relaxed
+// device-scope loads: other workgroups lower parent while this walk runs.
+__device__ __forceinline__ int root_of(const int32_t* parent, int x, int n)
+{
+    int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (p != x && in_range(p, n)) {
+        x = p;
+        p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return x;
+}
 
 // The headers' tree over the 256 values of a 256-thread workgroup (strides 128, 64, ... 1); every thread receives the total.
 template <typename T>

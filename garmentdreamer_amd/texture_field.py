@@ -391,6 +391,23 @@ class NeTFRenderer(MeshRenderer):
     mode sees torch's own synchronisation points, not a wait inside the solver library behind ``inv_ex``, which is not
     excluded by it.  A singular or non-finite pose raises, as in ``MeshRenderer``; it is detected on the host."""
 
+    @classmethod
+    def from_mesh(cls, vertices, indices, texture_fn, clean=True, min_faces=32, min_diameter_pct=10.0, **clean_args):
+        """The renderer of a mesh as it was loaded (``Renderer.__init__``, mesh_renderer.py:114-121): with ``clean`` the
+        mesh goes through ``mesh_clean.clean_mesh`` first, with the reference's ``min_f=32`` and ``min_d=10`` and
+        ``clean_args`` for the rest; ``vn`` are ``mesh_geometry.normals`` of what is left.  ``vertices`` float32 [V,3] and
+        ``indices`` [F,3] on the GPU; ``ValueError`` if cleaning leaves no face."""
+        from . import mesh_clean, mesh_geometry
+        v, f = vertices, indices
+        if clean:
+            cleaned = mesh_clean.clean_mesh(v, f, min_faces=min_faces, min_diameter_pct=min_diameter_pct, **clean_args)
+            v, f = cleaned.vertices, cleaned.indices
+            if f.shape[0] == 0:
+                raise ValueError("NeTFRenderer.from_mesh: cleaning left no face of the mesh")
+        v = require_gpu("NeTFRenderer.from_mesh", "vertices", v, torch.float32, 3).detach().contiguous()
+        geo = mesh_geometry.build_geometry(f, v.shape[0], v.device)
+        return cls(v, f, mesh_geometry.normals(v, geo)[1].detach(), texture_fn)
+
     def _matrices(self, pose, proj):
         """device float32 [3,4,4]: inverse pose, projection, pose"""
         pose = np.asarray(pose).astype(np.float32)
