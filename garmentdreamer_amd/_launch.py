@@ -1,5 +1,5 @@
-"""The one way from a torch tensor to an entry of ``libgd_raster.so``: what every op of the mesh, texture, bake and
-template modules does around its kernel, written once."""
+"""The one way from a torch tensor to an entry of ``libgd_raster.so`` or ``libgd_nn.so``: what every op does around its
+kernel, written once."""
 from __future__ import annotations
 
 from typing import Optional
@@ -9,14 +9,19 @@ import torch
 from . import _native
 
 
-def launch(name: str, dev, *args) -> int:
-    """Call the entry ``name`` on ``dev``'s current stream (its first argument) with ``args``, tensors as their
-    ``data_ptr()`` and everything else (``None``, numbers, ctypes values) as it is; raise with the entry's error text if
-    it fails.  Layout is the caller's business: nothing here copies, allocates or waits."""
-    fn = getattr(_native.lib(), name)
+def call(fn, dev, args):
+    """``fn`` on ``dev``'s current stream (its first argument) with ``args``, tensors as their ``data_ptr()`` and
+    everything else (``None``, numbers, ctypes values) as it is; returns what ``fn`` returns.  Layout is the caller's
+    business: nothing here copies, allocates or waits."""
     with torch.cuda.device(dev):
-        return _native.checked(name, fn(torch.cuda.current_stream(dev).cuda_stream,
-                                        *[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]))
+        return fn(torch.cuda.current_stream(dev).cuda_stream,
+                  *[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args])
+
+
+def launch(name: str, dev, *args) -> int:
+    """``call`` of the entry ``name`` of libgd_raster.so; raises with the entry's error text if it fails.
+    (``nn_ops.launch`` is the same for libgd_nn.so.)"""
+    return _native.checked(name, call(getattr(_native.lib(), name), dev, args))
 
 
 def scratch(nbytes: int, dev) -> torch.Tensor:

@@ -11,6 +11,8 @@ import weakref
 import torch
 import torch.nn.functional as F
 
+from ._launch import call as _call
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libgd_nn.so")
 _LIB_OVERRIDDEN = False
@@ -28,120 +30,138 @@ def use_library(path: str) -> None:
 
 
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
-SIGNATURES = {
-    "gd_nn_groupnorm_silu_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),
-    "gd_nn_groupnorm_silu_fused_supported": (_i, [_i, _i, _i, _i]),
-    "gd_nn_groupnorm_silu_fused_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i]),
-    "gd_nn_groupnorm_silu_fused_forward_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
-    "gd_nn_groupnorm_silu_fused_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_groupnorm_silu_fused_backward_supported": (_i, [_i, _i, _i, _i]),
-    "gd_nn_groupnorm_silu_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "gd_nn_groupnorm_ws_bytes": (C.c_size_t, [_i, _i]),
-    "gd_nn_conv3x3_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_ws_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_forward_ws": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t]),
-    "gd_nn_conv_force_split": (_i, [_i]),
-    "gd_nn_conv_set_route_scale": (_i, [_i]),
-    "gd_nn_conv3x3_flip_weights": (_i, [_vp, _vp, _vp, _i, _i]),
-    "gd_nn_conv3x3_first_dgrad_supported": (_i, [_i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_first_dgrad_weights": (_i, [_vp, _vp, _vp, _i, _i]),
-    "gd_nn_conv3x3_first_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_groupnorm_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
-    "gd_nn_groupnorm_silu_forward_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _f]),
-    "gd_nn_conv3x3_gn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_linear_320_supported": (_i, [C.c_int64, _i, _i]),
-    "gd_nn_linear_320_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
-    "gd_nn_linear_k320_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_linear_k320_geglu_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_linear_320_last_error": (C.c_char_p, []),
-    "gd_nn_conv3x3_stat_rows": (C.c_size_t, [_i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_first_stat_rows": (C.c_size_t, [_i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_first_forward_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "gd_nn_conv3x3_gn_forward_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i,
-                                            _vp]),
-    "gd_nn_conv3x3_forward_stats": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "gd_nn_conv3x3_wino_supported": (_i, [_i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_wino_weights": (_i, [_vp, _vp, _vp, _i, _i]),
-    "gd_nn_conv3x3_wino_weights_bytes": (C.c_size_t, [_i, _i]),
-    "gd_nn_conv3x3_wino_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "gd_nn_conv3x3_wino_gn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "gd_nn_conv3x3_wide_supported": (_i, [_i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_wide_weights": (_i, [_vp, _vp, _vp, _i, _i]),
-    "gd_nn_conv3x3_wide_weights_bytes": (C.c_size_t, [_i, _i]),
-    "gd_nn_conv3x3_wide_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "gd_nn_conv3x3_wide_gn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "gd_nn_groupnorm_finish_partials": (_i, [_vp, _vp, _i, C.c_size_t, _i, _i, _i, _f, _vp]),
-    "gd_nn_conv3x3_first_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_s2_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_s2_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_s2_ws_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
-    "gd_nn_conv3x3_s2_forward_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t]),
-    "gd_nn_conv3x3_s2_dgrad_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t]),
-    "gd_nn_conv3x3_up2_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_conv_force_variant": (_i, [_i]),
-    "gd_nn_linear_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
-    "gd_nn_gemm_supported": (_i, [C.c_int64, _i, _i, _i]),
-    "gd_nn_gemm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
-    "gd_nn_gemm_geglu_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
-    "gd_nn_gemm_last_error": (C.c_char_p, []),
-    "gd_nn_conv_profile_enable": (_i, [_i]),
-    "gd_nn_conv_profile_reset": (_i, []),
-    "gd_nn_conv_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
-    "gd_nn_conv_profile_read_bytes": (_i, [C.POINTER(C.c_double)]),
-    "gd_nn_geglu_forward": (_i, [_vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_geglu_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_conv1x1_c8": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_softmax_rows_forward": (_i, [_vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_softmax_rows_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_layernorm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float]),
-    "gd_nn_add_layernorm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_int64, _i]),
-    "gd_nn_add_layernorm_forward_bcast": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_int64, _i, C.c_int64]),
-    "gd_nn_join_stat_rows": (C.c_size_t, [_i, _i, _i]),
-    "gd_nn_add_gn_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
-    "gd_nn_concat_gn_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_attention_ws_bytes": (C.c_size_t, [_i, _i, _i]),
-    "gd_nn_attention_d64_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i,
-                                         C.c_int64, _i, C.c_int64, _i, _f, _i]),
-    "gd_nn_attention_d64_forward_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i,
+# error getter of a translation unit -> {entry defined in that unit: (restype, argtypes)}: each csrc/nn_*.hip keeps its own
+# thread-local message buffer (csrc/nn_host.h), so an entry's text is read from the getter it stands under here
+_UNITS = {
+    "gd_nn_last_error": {      # csrc/nn_groupnorm.hip
+        "gd_nn_groupnorm_silu_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+        "gd_nn_groupnorm_silu_fused_supported": (_i, [_i, _i, _i, _i]),
+        "gd_nn_groupnorm_silu_fused_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i]),
+        "gd_nn_groupnorm_silu_fused_forward_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+        "gd_nn_groupnorm_silu_fused_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_groupnorm_silu_fused_backward_supported": (_i, [_i, _i, _i, _i]),
+        "gd_nn_groupnorm_silu_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+        "gd_nn_groupnorm_ws_bytes": (C.c_size_t, [_i, _i]),
+        "gd_nn_groupnorm_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+        "gd_nn_groupnorm_silu_forward_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _f]),
+        "gd_nn_groupnorm_finish_partials": (_i, [_vp, _vp, _i, C.c_size_t, _i, _i, _i, _f, _vp]),
+    },
+    "gd_nn_conv_last_error": {      # csrc/nn_conv3x3.hip
+        "gd_nn_conv3x3_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_ws_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_forward_ws": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_size_t]),
+        "gd_nn_conv_force_split": (_i, [_i]),
+        "gd_nn_conv_set_route_scale": (_i, [_i]),
+        "gd_nn_conv3x3_flip_weights": (_i, [_vp, _vp, _vp, _i, _i]),
+        "gd_nn_conv3x3_first_dgrad_supported": (_i, [_i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_first_dgrad_weights": (_i, [_vp, _vp, _vp, _i, _i]),
+        "gd_nn_conv3x3_first_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_gn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_stat_rows": (C.c_size_t, [_i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_first_stat_rows": (C.c_size_t, [_i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_first_forward_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+        "gd_nn_conv3x3_gn_forward_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i,
+                                                _vp]),
+        "gd_nn_conv3x3_forward_stats": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+        "gd_nn_conv3x3_wino_supported": (_i, [_i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_wino_weights": (_i, [_vp, _vp, _vp, _i, _i]),
+        "gd_nn_conv3x3_wino_weights_bytes": (C.c_size_t, [_i, _i]),
+        "gd_nn_conv3x3_wino_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+        "gd_nn_conv3x3_wino_gn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+        "gd_nn_conv3x3_wide_supported": (_i, [_i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_wide_weights": (_i, [_vp, _vp, _vp, _i, _i]),
+        "gd_nn_conv3x3_wide_weights_bytes": (C.c_size_t, [_i, _i]),
+        "gd_nn_conv3x3_wide_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+        "gd_nn_conv3x3_wide_gn_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+        "gd_nn_conv3x3_first_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_s2_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_s2_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_s2_ws_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+        "gd_nn_conv3x3_s2_forward_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t]),
+        "gd_nn_conv3x3_s2_dgrad_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_size_t]),
+        "gd_nn_conv3x3_up2_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_conv_force_variant": (_i, [_i]),
+        "gd_nn_linear_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
+        "gd_nn_conv_profile_enable": (_i, [_i]),
+        "gd_nn_conv_profile_reset": (_i, []),
+        "gd_nn_conv_profile_read": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+        "gd_nn_conv_profile_read_bytes": (_i, [C.POINTER(C.c_double)]),
+    },
+    "gd_nn_linear_320_last_error": {      # csrc/nn_linear.hip
+        "gd_nn_linear_320_supported": (_i, [C.c_int64, _i, _i]),
+        "gd_nn_linear_320_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
+        "gd_nn_linear_k320_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_linear_k320_geglu_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i]),
+    },
+    "gd_nn_gemm_last_error": {      # csrc/nn_gemm.hip
+        "gd_nn_gemm_supported": (_i, [C.c_int64, _i, _i, _i]),
+        "gd_nn_gemm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
+        "gd_nn_gemm_geglu_forward": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
+    },
+    "gd_nn_elementwise_last_error": {      # csrc/nn_elementwise.hip
+        "gd_nn_geglu_forward": (_i, [_vp, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_geglu_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_conv1x1_c8": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_softmax_rows_forward": (_i, [_vp, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_softmax_rows_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_layernorm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float]),
+        "gd_nn_add_layernorm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_int64, _i]),
+        "gd_nn_add_layernorm_forward_bcast": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, C.c_int64, _i, C.c_int64]),
+        "gd_nn_join_stat_rows": (C.c_size_t, [_i, _i, _i]),
+        "gd_nn_add_gn_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+        "gd_nn_concat_gn_partials": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    },
+    "gd_nn_attention_last_error": {      # csrc/nn_attention.hip
+        "gd_nn_attention_ws_bytes": (C.c_size_t, [_i, _i, _i]),
+        "gd_nn_attention_d64_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i,
                                              C.c_int64, _i, C.c_int64, _i, _f, _i]),
-    "gd_nn_attention_bwd_ws_bytes": (C.c_size_t, [_i, _i, _i, _i]),
-    "gd_nn_attention_d64_backward": (_i, [_vp] * 11 + [_i, _i, _i, _i] + [C.c_int64, _i] * 8 + [_f, _i]),
-    "gd_nn_attention_d64_forward_vt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i, C.c_int64, _i,
-                                            _f]),
-    "gd_nn_attention_d64_forward_vt_strided": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i, C.c_int64,
-                                                    C.c_int64, _i, _f, _i]),
-    "gd_nn_attention_last_error": (C.c_char_p, []),
-    "gd_nn_vae_prologue_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_vae_prologue_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
-    "gd_nn_sparsity_forward": (_i, [_vp, _vp, _vp, C.c_int64, _vp]),
-    "gd_nn_sparsity_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
-    "gd_nn_prologue_last_error": (C.c_char_p, []),
-    "gd_nn_fp8_quantize": (_i, [_vp, _vp, _vp, C.c_int64, _f]),
-    "gd_nn_fp8_pack_weights": (_i, [_vp, _vp, _vp, C.c_int64, _i, _i, _f]),
-    "gd_nn_fp8_linear_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _f]),
-    "gd_nn_fp8_conv3x3_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f]),
-    "gd_nn_fp8_last_error": (C.c_char_p, []),
-    "gd_nn_conv_last_error": (C.c_char_p, []),
-    "gd_nn_elementwise_last_error": (C.c_char_p, []),
-    "gd_nn_lora_rowdot": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float, _i]),
-    "gd_nn_lora_rank4_add": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
-    "gd_nn_lora_row_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, C.c_float, _i]),
-    "gd_nn_lora_colreduce_scratch_floats": (C.c_size_t, [C.c_int64, _i]),
-    "gd_nn_lora_colreduce": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float, _i]),
-    "gd_nn_lora_colreduce_pair_scratch_floats": (C.c_size_t, [C.c_int64, _i, _i]),
-    "gd_nn_lora_colreduce_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
-    "gd_nn_lora_colreduce_pair_into": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i]),
-    "gd_nn_lora_colreduce_group_entry_bytes": (C.c_size_t, []),
-    "gd_nn_lora_colreduce_group_desc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, C.POINTER(C.c_int)]),
-    "gd_nn_lora_colreduce_group_launch": (_i, [_vp, _vp, _i, _i, _i, _i]),
-    "gd_nn_lora_last_error": (C.c_char_p, []),
-    "gd_nn_vae_decoder_stem_supported": (_i, [_i, _i, _i, _i]),
-    "gd_nn_vae_decoder_stem": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
-    "gd_nn_vae_decoder_head_supported": (_i, [_i, _i, _i, _i, _i]),
-    "gd_nn_vae_decoder_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
-    "gd_nn_vae_decoder_last_error": (C.c_char_p, []),
-    "gd_nn_last_error": (C.c_char_p, []),
+        "gd_nn_attention_d64_forward_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i,
+                                                 C.c_int64, _i, C.c_int64, _i, _f, _i]),
+        "gd_nn_attention_bwd_ws_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+        "gd_nn_attention_d64_backward": (_i, [_vp] * 11 + [_i, _i, _i, _i] + [C.c_int64, _i] * 8 + [_f, _i]),
+        "gd_nn_attention_d64_forward_vt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i, C.c_int64, _i,
+                                                _f]),
+        "gd_nn_attention_d64_forward_vt_strided": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_int64, _i, C.c_int64, _i,
+                                                        C.c_int64, C.c_int64, _i, _f, _i]),
+    },
+    "gd_nn_prologue_last_error": {      # csrc/nn_prologue.hip
+        "gd_nn_vae_prologue_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
+        "gd_nn_vae_prologue_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
+        "gd_nn_sparsity_forward": (_i, [_vp, _vp, _vp, C.c_int64, _vp]),
+        "gd_nn_sparsity_backward": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    },
+    "gd_nn_fp8_last_error": {      # csrc/nn_fp8.hip
+        "gd_nn_fp8_quantize": (_i, [_vp, _vp, _vp, C.c_int64, _f]),
+        "gd_nn_fp8_pack_weights": (_i, [_vp, _vp, _vp, C.c_int64, _i, _i, _f]),
+        "gd_nn_fp8_linear_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, _f]),
+        "gd_nn_fp8_conv3x3_forward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f]),
+    },
+    "gd_nn_lora_last_error": {      # csrc/nn_lora.hip
+        "gd_nn_lora_rowdot": (_i, [_vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float, _i]),
+        "gd_nn_lora_rank4_add": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
+        "gd_nn_lora_row_fused": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, C.c_float, _i]),
+        "gd_nn_lora_colreduce_scratch_floats": (C.c_size_t, [C.c_int64, _i]),
+        "gd_nn_lora_colreduce": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _i, C.c_float, _i]),
+        "gd_nn_lora_colreduce_pair_scratch_floats": (C.c_size_t, [C.c_int64, _i, _i]),
+        "gd_nn_lora_colreduce_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i]),
+        "gd_nn_lora_colreduce_pair_into": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i]),
+        "gd_nn_lora_colreduce_group_entry_bytes": (C.c_size_t, []),
+        "gd_nn_lora_colreduce_group_desc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _i, _i, C.POINTER(C.c_int)]),
+        "gd_nn_lora_colreduce_group_launch": (_i, [_vp, _vp, _i, _i, _i, _i]),
+    },
+    "gd_nn_vae_decoder_last_error": {      # csrc/nn_vae_decoder.hip
+        "gd_nn_vae_decoder_stem_supported": (_i, [_i, _i, _i, _i]),
+        "gd_nn_vae_decoder_stem": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+        "gd_nn_vae_decoder_head_supported": (_i, [_i, _i, _i, _i, _i]),
+        "gd_nn_vae_decoder_head": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    },
 }
+# symbol -> (restype, argtypes), mirrors include/gd_nn.h one to one; entry -> the getter of its unit
+SIGNATURES = {getter: (C.c_char_p, []) for getter in _UNITS}
+_ERROR_CHANNEL = {}
+for _getter, _entries in _UNITS.items():
+    SIGNATURES.update(_entries)
+    _ERROR_CHANNEL.update(dict.fromkeys(_entries, _getter))
 
 
 def lib():
@@ -163,11 +183,25 @@ def lib():
     return _lib
 
 
-def _check(ret, what, err="gd_nn_last_error"):
-    """``err`` names the error-text getter of the translation unit ``what`` lives in (each csrc file keeps its own
-    thread-local buffer: gd_nn_last_error is the GroupNorm file's)."""
+def error_channel(name: str) -> str:
+    """The ``gd_nn_*_last_error`` getter defined in the same csrc file as the entry ``name``."""
+    return _ERROR_CHANNEL[name]
+
+
+def _check(ret, what, err=None):
+    """``ret`` if it is not negative, else ``RuntimeError`` with the text of ``err``: by default the getter of the
+    translation unit the entry ``what`` lives in (the GroupNorm file's gd_nn_last_error for a name that is no entry)."""
     if ret < 0:
-        raise RuntimeError(f"{what} failed ({ret}): {getattr(lib(), err)().decode()}")
+        text = getattr(lib(), err or _ERROR_CHANNEL.get(what, "gd_nn_last_error"))().decode("utf-8", "replace")
+        raise RuntimeError(f"{what} failed ({ret}): {text}")
+    return ret
+
+
+def launch(name: str, dev, *args) -> int:
+    """``_launch.launch`` for libgd_nn.so: the entry ``name`` on ``dev``'s current stream with ``args``, tensors as
+    their ``data_ptr()``; raises with the text of the entry's own error channel if it fails.  Nothing here copies,
+    allocates or waits."""
+    return _check(_call(getattr(lib(), name), dev, args), name)
 
 
 _gn_ws_cache = {}
@@ -247,22 +281,33 @@ def _is_nhwc_bf16(x):
     return x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
 
 
+def _grad_nhwc_bf16(dy):
+    """The incoming gradient of a backward as the kernels read it: channels_last, bf16."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    return dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16)
+
+
+def _derived(weight, attr, build):
+    """``build()`` cached on ``weight`` as ``attr`` (its key as ``attr + "_key"``): rebuilt after load_state_dict / an
+    in-place edit of the weight (``_version``), another storage or another device.  A value derived from another
+    derived value (``_gd_flipped_pad`` from ``_gd_flipped``) needs no key of its own: both are rebuilt under this one."""
+    key = (weight.data_ptr(), weight._version, weight.device)
+    if getattr(weight, attr, None) is None or getattr(weight, attr + "_key", None) != key:
+        setattr(weight, attr, build())
+        setattr(weight, attr + "_key", key)
+    return getattr(weight, attr)
+
+
 class _GroupNormSiLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, groups, eps, silu, mean_rstd=None):
         N, Cc, H, W = x.shape
-        L = lib()
         y = torch.empty_like(x, memory_format=torch.channels_last)
         # mean_rstd given: the statistics came with the tensor (a join's or a convolution's partial sums) -- apply pass only
         ws = _gn_workspace(x, N, groups) if mean_rstd is None else None
         mr = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device) if mean_rstd is None else mean_rstd
         w, b = weight.contiguous(), bias.contiguous()
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _check(L.gd_nn_groupnorm_silu_forward(stream, x.data_ptr(), y.data_ptr(), w.data_ptr(), b.data_ptr(), N,
-                                                  H * W, Cc, groups, float(eps), int(silu),
-                                                  None if ws is None else ws.data_ptr(), mr.data_ptr()),
-                   "gd_nn_groupnorm_silu_forward")
+        launch("gd_nn_groupnorm_silu_forward", x.device, x, y, w, b, N, H * W, Cc, groups, float(eps), int(silu), ws, mr)
         ctx.save_for_backward(x, w, b, mr)
         ctx.groups, ctx.silu = groups, silu
         return y
@@ -270,21 +315,7 @@ class _GroupNormSiLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, b, mr = ctx.saved_tensors
-        N, Cc, H, W = x.shape
-        L = lib()
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dx = torch.empty_like(x, memory_format=torch.channels_last)
-        ws = _gn_workspace(x, N, ctx.groups)
-        sums = torch.empty(N * ctx.groups * 2, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _check(L.gd_nn_groupnorm_silu_backward(stream, x.data_ptr(), dy.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                                   mr.data_ptr(), dx.data_ptr(), N, H * W, Cc, ctx.groups,
-                                                   int(ctx.silu), ws.data_ptr(), sums.data_ptr(), None),
-                   "gd_nn_groupnorm_silu_backward")
-        return dx, None, None, None, None, None, None
+        return _gn_bwd_launch(x, _grad_nhwc_bf16(dy), w, b, mr, ctx.groups, ctx.silu), None, None, None, None, None, None
 
 
 # GD_NN_GN_SMALL=0: the two-pass GroupNorm also where the one-launch form applies (A/B timing in tools/; never set in tests)
@@ -296,10 +327,7 @@ def _gn_fused_small(x, weight, bias, groups, eps, silu):
     N, Cc, H, W = x.shape
     y = torch.empty_like(x, memory_format=torch.channels_last)
     w, b = weight.contiguous(), bias.contiguous()
-    with torch.cuda.device(x.device):
-        _check(lib().gd_nn_groupnorm_silu_fused_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-                                                        y.data_ptr(), w.data_ptr(), b.data_ptr(), N, H * W, Cc, groups,
-                                                        float(eps), int(silu)), "gd_nn_groupnorm_silu_fused_forward")
+    launch("gd_nn_groupnorm_silu_fused_forward", x.device, x, y, w, b, N, H * W, Cc, groups, float(eps), int(silu))
     return y
 
 
@@ -317,10 +345,8 @@ class _GroupNormSiLUSmall(torch.autograd.Function):
         y = torch.empty_like(x, memory_format=torch.channels_last)
         mr = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
         w, b = weight.contiguous(), bias.contiguous()
-        with torch.cuda.device(x.device):
-            _check(lib().gd_nn_groupnorm_silu_fused_forward_stats(
-                torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), y.data_ptr(), w.data_ptr(), b.data_ptr(), N,
-                H * W, Cc, groups, float(eps), int(silu), mr.data_ptr()), "gd_nn_groupnorm_silu_fused_forward_stats")
+        launch("gd_nn_groupnorm_silu_fused_forward_stats", x.device, x, y, w, b, N, H * W, Cc, groups, float(eps), int(silu),
+               mr)
         ctx.save_for_backward(x, w, b, mr)
         ctx.groups, ctx.silu = groups, silu
         return y
@@ -329,24 +355,13 @@ class _GroupNormSiLUSmall(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, b, mr = ctx.saved_tensors
         N, Cc, H, W = x.shape
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dx = torch.empty_like(x, memory_format=torch.channels_last)
-        L = lib()
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            if L.gd_nn_groupnorm_silu_fused_backward_supported(N, H * W, Cc, ctx.groups):
-                _check(L.gd_nn_groupnorm_silu_fused_backward(stream, x.data_ptr(), dy.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                                             mr.data_ptr(), dx.data_ptr(), N, H * W, Cc, ctx.groups,
-                                                             int(ctx.silu)), "gd_nn_groupnorm_silu_fused_backward")
-            else:       # x and dy of the slice do not fit the registers together: the two-pass pair on the kept statistics
-                ws = _gn_workspace(x, N, ctx.groups)
-                sums = torch.empty(N * ctx.groups * 2, dtype=torch.float32, device=x.device)
-                _check(L.gd_nn_groupnorm_silu_backward(stream, x.data_ptr(), dy.data_ptr(), w.data_ptr(), b.data_ptr(),
-                                                       mr.data_ptr(), dx.data_ptr(), N, H * W, Cc, ctx.groups,
-                                                       int(ctx.silu), ws.data_ptr(), sums.data_ptr(), None),
-                       "gd_nn_groupnorm_silu_backward")
+        dy = _grad_nhwc_bf16(dy)
+        if lib().gd_nn_groupnorm_silu_fused_backward_supported(N, H * W, Cc, ctx.groups):
+            dx = torch.empty_like(x, memory_format=torch.channels_last)
+            launch("gd_nn_groupnorm_silu_fused_backward", x.device, x, dy, w, b, mr, dx, N, H * W, Cc, ctx.groups,
+                   int(ctx.silu))
+        else:       # x and dy of the slice do not fit the registers together: the two-pass pair on the kept statistics
+            dx = _gn_bwd_launch(x, dy, w, b, mr, ctx.groups, ctx.silu)
         return dx, None, None, None, None, None
 
 
@@ -433,21 +448,15 @@ def _join(a, b, concat: bool, next_norm, stats=None):
         stats = G > 0 and next_norm.num_channels == Cc and Cc % G == 0 and (Cc // G) % 4 == 0
     rows = L.gd_nn_join_stat_rows(N, H * W, Cc) if stats else 0
     part = torch.empty(N * (Cc // 4) * rows * 2, dtype=torch.float32, device=a.device) if rows else None
-    with torch.cuda.device(a.device):
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        part_p = None if part is None else part.data_ptr()
-        if concat:
-            ret = L.gd_nn_concat_gn_partials(stream, a.data_ptr(), b.data_ptr(), out.data_ptr(), part_p, N, b.shape[0], H * W,
-                                             C0, C1)
-        else:
-            ret = L.gd_nn_add_gn_partials(stream, a.data_ptr(), b.data_ptr(), out.data_ptr(), part_p, N, b.shape[0], H * W, C0)
-        _check(ret, "gd_nn_concat_gn_partials" if concat else "gd_nn_add_gn_partials", "gd_nn_elementwise_last_error")
-        if part is not None:
-            G, eps = next_norm.num_groups, next_norm.eps
-            mr = torch.empty(N * G * 2, dtype=torch.float32, device=a.device)
-            _check(L.gd_nn_groupnorm_finish_partials(stream, part.data_ptr(), N, rows, Cc, G, H * W, float(eps), mr.data_ptr()),
-                   "gd_nn_groupnorm_finish_partials")
-            out._gd_gn_stats = (mr, G, eps, out._version)
+    if concat:
+        launch("gd_nn_concat_gn_partials", a.device, a, b, out, part, N, b.shape[0], H * W, C0, C1)
+    else:
+        launch("gd_nn_add_gn_partials", a.device, a, b, out, part, N, b.shape[0], H * W, C0)
+    if part is not None:
+        G, eps = next_norm.num_groups, next_norm.eps
+        mr = torch.empty(N * G * 2, dtype=torch.float32, device=a.device)
+        launch("gd_nn_groupnorm_finish_partials", a.device, part, N, rows, Cc, G, H * W, float(eps), mr)
+        out._gd_gn_stats = (mr, G, eps, out._version)
     return out
 
 
@@ -619,21 +628,14 @@ def _conv_launch(x, w_khwc, bias, residual, out_channels):
     route = _conv_route(N, H, W, Cin, out_channels)
     if route is not None:
         return _tiled_launch(route, x, w_khwc, bias, residual, out_channels)
-    L = lib()
     y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device,
                     memory_format=torch.channels_last)
     bias, stride = _bias_and_stride(bias)
     # small-M layers run split over the taps and need fp32 scratch (torch's allocator: hipGraph-capture safe)
-    ws_bytes = L.gd_nn_conv3x3_ws_bytes(N, H, W, Cin, out_channels)
+    ws_bytes = lib().gd_nn_conv3x3_ws_bytes(N, H, W, Cin, out_channels)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ret = L.gd_nn_conv3x3_forward_ws(stream, x.data_ptr(), w_khwc.data_ptr(),
-                                         None if bias is None else bias.data_ptr(), stride,
-                                         None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W, Cin,
-                                         out_channels, None if ws is None else ws.data_ptr(), ws_bytes)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_conv3x3_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+    launch("gd_nn_conv3x3_forward_ws", x.device, x, w_khwc, bias, stride, residual, y, N, H, W, Cin, out_channels, ws,
+           ws_bytes)
     return y
 
 
@@ -641,20 +643,13 @@ def _packed(weight, kind):
     """Cached filter bank of a frozen conv weight (channels_last, i.e. [Cout][3][3][Cin] in memory -- also of a flipped
     dgrad weight tensor) in the step images of a tiled kernel (include/gd_nn.h): kind "wino" = Winograd F(2,3), 32 KB
     each; "wide" = the wide-tile kernel's re-packing, 24 KB each."""
-    attr = "_gd_" + kind
-    u = getattr(weight, attr, None)
-    key = (weight.data_ptr(), weight._version)
-    if u is None or u.device != weight.device or getattr(weight, attr + "_key", None) != key:
-        L, name = lib(), f"gd_nn_conv3x3_{kind}_weights"
+    def build():
+        name = f"gd_nn_conv3x3_{kind}_weights"
         Cout, Cin = weight.shape[0], weight.shape[1]
-        u = torch.empty(getattr(L, name + "_bytes")(Cout, Cin) // 2, dtype=torch.bfloat16, device=weight.device)
-        with torch.cuda.device(weight.device):
-            ret = getattr(L, name)(torch.cuda.current_stream(weight.device).cuda_stream, weight.data_ptr(), u.data_ptr(),
-                                   Cout, Cin)
-        _check(ret, name, "gd_nn_conv_last_error")
-        setattr(weight, attr, u)
-        setattr(weight, attr + "_key", key)
-    return u
+        u = torch.empty(getattr(lib(), name + "_bytes")(Cout, Cin) // 2, dtype=torch.bfloat16, device=weight.device)
+        launch(name, weight.device, weight, u, Cout, Cin)
+        return u
+    return _derived(weight, "_gd_" + kind, build)
 
 
 # C entries of the tiled kernels: (plain, GroupNorm in the loader); both take the statistics buffer last
@@ -669,26 +664,20 @@ def _tiled_launch(kind, x, w_khwc, bias, residual, out_channels, stat_part=None,
     gamma, beta, groups, silu) applies GroupNorm(+SiLU) in the loader, ``mean_rstd`` from gd_nn_groupnorm_stats /
     finish_partials; ``stat_part`` receives the epilogue's partial sums (gd_nn_conv3x3_stat_rows)."""
     N, Cin, H, W = x.shape
-    L = lib()
     y = torch.empty((N, out_channels, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
     bias, stride = _bias_and_stride(bias)
     wp = w_khwc if kind == "patch" else _packed(w_khwc, kind)
     plain_name, gn_name = _TILED_ENTRY[kind]
     if gn is not None:
         mr, gw, gb, groups, silu = gn
-        name, head = gn_name, (mr.data_ptr(), gw.data_ptr(), gb.data_ptr(), groups, int(silu))
+        name, head = gn_name, (mr, gw, gb, groups, int(silu))
     elif kind == "patch" and stat_part is None:
         # the patch kernel's plain entry insists on statistics and on its own routing rule: without statistics, its
         # GroupNorm entry with no GroupNorm (the same launch as gd_nn_conv3x3_gn_forward)
         name, head = gn_name, (None, None, None, 0, 0)
     else:
         name, head = plain_name, ()
-    with torch.cuda.device(x.device):
-        ret = getattr(L, name)(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), *head, wp.data_ptr(),
-                               None if bias is None else bias.data_ptr(), stride,
-                               None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W, Cin, out_channels,
-                               None if stat_part is None else stat_part.data_ptr())
-    _check(ret, name, "gd_nn_conv_last_error")
+    launch(name, x.device, x, *head, wp, bias, stride, residual, y, N, H, W, Cin, out_channels, stat_part)
     return y
 
 
@@ -710,20 +699,13 @@ def _wino_gn_launch(x, mean_rstd, gn_weight, gn_bias, groups, silu, w_khwc, bias
 
 def _flipped(weight):
     """Cached dgrad weights [Cin][3][3][Cout] for a frozen conv weight (stored channels_last)."""
-    f = getattr(weight, "_gd_flipped", None)
-    key = (weight.data_ptr(), weight._version)      # re-derive after load_state_dict / in-place edits of the weight
-    if f is None or f.device != weight.device or getattr(weight, "_gd_flipped_key", None) != key:
+    def build():
         Cout, Cin = weight.shape[0], weight.shape[1]
         f = torch.empty((Cin, Cout, 3, 3), dtype=torch.bfloat16, device=weight.device,
                         memory_format=torch.channels_last)
-        L = lib()
-        with torch.cuda.device(weight.device):
-            ret = L.gd_nn_conv3x3_flip_weights(torch.cuda.current_stream(weight.device).cuda_stream,
-                                               weight.data_ptr(), f.data_ptr(), Cout, Cin)
-        if ret < 0:
-            raise RuntimeError("gd_nn_conv3x3_flip_weights failed")
-        weight._gd_flipped, weight._gd_flipped_key = f, key
-    return f
+        launch("gd_nn_conv3x3_flip_weights", weight.device, weight, f, Cout, Cin)
+        return f
+    return _derived(weight, "_gd_flipped", build)
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -737,9 +719,7 @@ class _Conv3x3(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         w = ctx.weight
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _grad_nhwc_bf16(dy)
         dx = None
         if ctx.needs_input_grad[0]:
             if w.shape[0] % 64 == 0:
@@ -749,13 +729,13 @@ class _Conv3x3(torch.autograd.Function):
                 # one 64-channel K-step instead of handing the layer to MIOpen
                 Cout, Cp = w.shape[0], (w.shape[0] + 63) // 64 * 64
                 f = _flipped(w)
-                key = (f.data_ptr(), w._version)
-                fp = getattr(w, "_gd_flipped_pad", None)
-                if fp is None or getattr(w, "_gd_flipped_pad_key", None) != key:
+
+                def padded():
                     fp = torch.zeros((w.shape[1], Cp, 3, 3), dtype=torch.bfloat16, device=w.device).contiguous(
                         memory_format=torch.channels_last)
                     fp[:, :Cout] = f
-                    w._gd_flipped_pad, w._gd_flipped_pad_key = fp, key
+                    return fp
+                fp = _derived(w, "_gd_flipped_pad", padded)
                 dyp = torch.zeros((dy.shape[0], Cp) + tuple(dy.shape[2:]), dtype=torch.bfloat16, device=dy.device).contiguous(
                     memory_format=torch.channels_last)
                 dyp[:, :Cout] = dy
@@ -790,28 +770,18 @@ class _ConvSmallCin(torch.autograd.Function):
             xc = x.contiguous(memory_format=torch.channels_last)
             wc = weight.contiguous(memory_format=torch.channels_last)
             y = torch.empty((N, Cout, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-            L = lib()
             rows = 0
             if next_norm is not None and _EPILOGUE_STATS and Cout % (4 * next_norm[0]) == 0:
-                rows = L.gd_nn_conv3x3_first_stat_rows(N, H, W, Cin, Cout)
+                rows = lib().gd_nn_conv3x3_first_stat_rows(N, H, W, Cin, Cout)
             mr_next = None
-            with torch.cuda.device(x.device):
-                stream = torch.cuda.current_stream(x.device).cuda_stream
-                bias_p = None if bias is None else bias.data_ptr()
-                if rows:
-                    part = torch.empty(N * (Cout // 4) * rows * 2, dtype=torch.float32, device=x.device)
-                    ret = L.gd_nn_conv3x3_first_forward_stats(stream, xc.data_ptr(), wc.data_ptr(), bias_p, y.data_ptr(),
-                                                              N, H, W, Cin, Cout, part.data_ptr())
-                else:
-                    ret = L.gd_nn_conv3x3_first_forward(stream, xc.data_ptr(), wc.data_ptr(), bias_p, y.data_ptr(), N, H,
-                                                        W, Cin, Cout)
-                if ret < 0:
-                    raise RuntimeError(f"gd_nn_conv3x3_first_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
-                if rows:
-                    mr_next = torch.empty(N * next_norm[0] * 2, dtype=torch.float32, device=x.device)
-                    _check(L.gd_nn_groupnorm_finish_partials(stream, part.data_ptr(), N, rows, Cout, next_norm[0], H * W,
-                                                             float(next_norm[1]), mr_next.data_ptr()),
-                           "gd_nn_groupnorm_finish_partials")
+            if rows:
+                part = torch.empty(N * (Cout // 4) * rows * 2, dtype=torch.float32, device=x.device)
+                launch("gd_nn_conv3x3_first_forward_stats", x.device, xc, wc, bias, y, N, H, W, Cin, Cout, part)
+                mr_next = torch.empty(N * next_norm[0] * 2, dtype=torch.float32, device=x.device)
+                launch("gd_nn_groupnorm_finish_partials", x.device, part, N, rows, Cout, next_norm[0], H * W,
+                       float(next_norm[1]), mr_next)
+            else:
+                launch("gd_nn_conv3x3_first_forward", x.device, xc, wc, bias, y, N, H, W, Cin, Cout)
             if mr_next is not None:
                 ctx.mark_non_differentiable(mr_next)
             return y, mr_next
@@ -829,34 +799,24 @@ class _ConvSmallCin(torch.autograd.Function):
         if _FIRST_DGRAD and dy.dtype == torch.bfloat16 and lib().gd_nn_conv3x3_first_dgrad_supported(N, H, W, Cin, Cout):
             # round 5: dy read once -- a 128 -> 9 x 3 product per pixel on the matrix cores, the nine shifted partial results summed
             # through LDS (csrc/nn_conv_first_dgrad.h); the padded implicit-GEMM form below read every dy element nine times
-            wp = getattr(w, "_gd_first_dgrad", None)
-            key = (w.data_ptr(), w._version)
-            L = lib()
+            def packed():
+                wp = torch.empty(32 * 128, dtype=torch.bfloat16, device=w.device)
+                wc = w.contiguous(memory_format=torch.channels_last)
+                launch("gd_nn_conv3x3_first_dgrad_weights", w.device, wc, wp, Cout, Cin)
+                return wp
             dy = dy.contiguous(memory_format=torch.channels_last)
-            with torch.cuda.device(w.device):
-                stream = torch.cuda.current_stream(w.device).cuda_stream
-                if wp is None or wp.device != w.device or getattr(w, "_gd_first_dgrad_key", None) != key:
-                    wp = torch.empty(32 * 128, dtype=torch.bfloat16, device=w.device)
-                    wc = w.contiguous(memory_format=torch.channels_last)
-                    _check(L.gd_nn_conv3x3_first_dgrad_weights(stream, wc.data_ptr(), wp.data_ptr(), Cout, Cin),
-                           "gd_nn_conv3x3_first_dgrad_weights", "gd_nn_conv_last_error")
-                    w._gd_first_dgrad, w._gd_first_dgrad_key = wp, key
-                dx4 = torch.empty((N, 4, H, W), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
-                _check(L.gd_nn_conv3x3_first_dgrad(stream, dy.data_ptr(), wp.data_ptr(), dx4.data_ptr(), N, H, W, Cin, Cout),
-                       "gd_nn_conv3x3_first_dgrad", "gd_nn_conv_last_error")
+            wp = _derived(w, "_gd_first_dgrad", packed)
+            dx4 = torch.empty((N, 4, H, W), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
+            launch("gd_nn_conv3x3_first_dgrad", w.device, dy, wp, dx4, N, H, W, Cin, Cout)
             return dx4[:, :Cin], None, None, None
-        f = getattr(w, "_gd_flipped4", None)
-        key = (w.data_ptr(), w._version)
-        if f is None or f.device != w.device or getattr(w, "_gd_flipped4_key", None) != key:
+
+        def flipped4():
             f = torch.zeros((4, Cout, 3, 3), dtype=torch.bfloat16, device=w.device).contiguous(
                 memory_format=torch.channels_last)
             wc = w.contiguous(memory_format=torch.channels_last)
-            with torch.cuda.device(w.device):
-                ret = lib().gd_nn_conv3x3_flip_weights(torch.cuda.current_stream(w.device).cuda_stream, wc.data_ptr(),
-                                                       f.data_ptr(), Cout, Cin)
-            if ret < 0:
-                raise RuntimeError("gd_nn_conv3x3_flip_weights failed")
-            w._gd_flipped4, w._gd_flipped4_key = f, key
+            launch("gd_nn_conv3x3_flip_weights", w.device, wc, f, Cout, Cin)
+            return f
+        f = _derived(w, "_gd_flipped4", flipped4)
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx4 = _conv_launch(dy, f, None, None, 4)
         return dx4[:, :Cin], None, None, None
@@ -939,22 +899,14 @@ class _GNConv3x3(torch.autograd.Function):
     def forward(ctx, x, gn_weight, gn_bias, groups, eps, silu, weight, bias, residual):
         N, Cin, H, W = x.shape
         Cout = weight.shape[0]
-        L = lib()
         ws = _gn_workspace(x, N, groups)
         mr = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
         y = torch.empty((N, Cout, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
         gw, gb = gn_weight.contiguous(), gn_bias.contiguous()
         bias, stride = _bias_and_stride(bias)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            _check(L.gd_nn_groupnorm_stats(stream, x.data_ptr(), N, H * W, Cin, groups, float(eps), ws.data_ptr(),
-                                           mr.data_ptr()), "gd_nn_groupnorm_stats")
-            ret = L.gd_nn_conv3x3_gn_forward(stream, x.data_ptr(), mr.data_ptr(), gw.data_ptr(), gb.data_ptr(), groups,
-                                             int(silu), weight.data_ptr(), None if bias is None else bias.data_ptr(),
-                                             stride, None if residual is None else residual.data_ptr(), y.data_ptr(),
-                                             N, H, W, Cin, Cout)
-        if ret < 0:
-            raise RuntimeError(f"gd_nn_conv3x3_gn_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+        launch("gd_nn_groupnorm_stats", x.device, x, N, H * W, Cin, groups, float(eps), ws, mr)
+        launch("gd_nn_conv3x3_gn_forward", x.device, x, mr, gw, gb, groups, int(silu), weight, bias, stride, residual, y,
+               N, H, W, Cin, Cout)
         ctx.save_for_backward(x, gw, gb, mr)
         ctx.weight, ctx.groups, ctx.silu, ctx.has_res = weight, groups, silu, residual is not None
         return y
@@ -963,24 +915,11 @@ class _GNConv3x3(torch.autograd.Function):
     def backward(ctx, dy):
         x, gw, gb, mr = ctx.saved_tensors
         w = ctx.weight
-        N, Cin, H, W = x.shape
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _grad_nhwc_bf16(dy)
         dx = None
         if ctx.needs_input_grad[0]:
-            dact = _conv_launch(dy, _flipped(w), None, None, Cin)          # gradient w.r.t. act(GN(x))
-            dx = torch.empty_like(x, memory_format=torch.channels_last)
-            ws = _gn_workspace(x, N, ctx.groups)
-            sums = torch.empty(N * ctx.groups * 2, dtype=torch.float32, device=x.device)
-            L = lib()
-            with torch.cuda.device(x.device):
-                stream = torch.cuda.current_stream(x.device).cuda_stream
-                _check(L.gd_nn_groupnorm_silu_backward(stream, x.data_ptr(), dact.data_ptr(), gw.data_ptr(),
-                                                       gb.data_ptr(), mr.data_ptr(), dx.data_ptr(), N, H * W, Cin,
-                                                       ctx.groups, int(ctx.silu), ws.data_ptr(), sums.data_ptr(),
-                                                       None),
-                       "gd_nn_groupnorm_silu_backward")
+            dact = _conv_launch(dy, _flipped(w), None, None, x.shape[1])   # gradient w.r.t. act(GN(x))
+            dx = _gn_bwd_launch(x, dact, gw, gb, mr, ctx.groups, ctx.silu)
         return dx, None, None, None, None, None, None, None, (dy if ctx.has_res else None)
 
 
@@ -1023,12 +962,7 @@ def _gn_bwd_launch(x, dy, gw, gb, mr, groups, silu, add=None):
     dx = torch.empty_like(x, memory_format=torch.channels_last)
     ws = _gn_workspace(x, N, groups)
     sums = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gd_nn_groupnorm_silu_backward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-                                                   dy.data_ptr(), gw.data_ptr(), gb.data_ptr(), mr.data_ptr(),
-                                                   dx.data_ptr(), N, H * W, Cc, groups, int(silu), ws.data_ptr(),
-                                                   sums.data_ptr(), None if add is None else add.data_ptr()),
-               "gd_nn_groupnorm_silu_backward")
+    launch("gd_nn_groupnorm_silu_backward", x.device, x, dy, gw, gb, mr, dx, N, H * W, Cc, groups, int(silu), ws, sums, add)
     return dx
 
 
@@ -1050,28 +984,22 @@ def _gnconv_forward(x, gw, gb, groups, eps, w, bias, residual, mr=None, next_nor
     if next_norm is not None and _EPILOGUE_STATS and Cout % next_norm[0] == 0 and (Cout // next_norm[0]) % 4 == 0:
         rows = L.gd_nn_conv3x3_stat_rows(N, H, W, Cout, int(fused))
     part = torch.empty(N * (Cout // 4) * rows * 2, dtype=torch.float32, device=x.device) if rows else None
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        if fused:
-            if not have_mr:
-                _check(L.gd_nn_groupnorm_stats(stream, x.data_ptr(), N, H * W, Cin, groups, float(eps), ws.data_ptr(),
-                                               mr.data_ptr()), "gd_nn_groupnorm_stats")
-            kind = "wide" if _conv_route(N, H, W, Cin, Cout, gn=True) == "wide" else "patch"
-            y = _tiled_launch(kind, x, w, bias, residual, Cout, part, (mr, gw, gb, groups, True))
-        else:
-            act = torch.empty_like(x, memory_format=torch.channels_last)
-            _check(L.gd_nn_groupnorm_silu_forward(stream, x.data_ptr(), act.data_ptr(), gw.data_ptr(), gb.data_ptr(), N,
-                                                  H * W, Cin, groups, float(eps), 1, None if have_mr else ws.data_ptr(),
-                                                  mr.data_ptr()), "gd_nn_groupnorm_silu_forward")
-            if part is None:
-                return _conv_launch(act, w, bias, residual, Cout), mr, None
-            y = _tiled_launch(_conv_route(N, H, W, Cin, Cout) or "patch", act, w, bias, residual, Cout, part)
-        mr_next = None
-        if part is not None:
-            g2, eps2 = next_norm
-            mr_next = torch.empty(N * g2 * 2, dtype=torch.float32, device=x.device)
-            _check(L.gd_nn_groupnorm_finish_partials(stream, part.data_ptr(), N, rows, Cout, g2, H * W, float(eps2),
-                                                     mr_next.data_ptr()), "gd_nn_groupnorm_finish_partials")
+    if fused:
+        if not have_mr:
+            launch("gd_nn_groupnorm_stats", x.device, x, N, H * W, Cin, groups, float(eps), ws, mr)
+        kind = "wide" if _conv_route(N, H, W, Cin, Cout, gn=True) == "wide" else "patch"
+        y = _tiled_launch(kind, x, w, bias, residual, Cout, part, (mr, gw, gb, groups, True))
+    else:
+        act = torch.empty_like(x, memory_format=torch.channels_last)
+        launch("gd_nn_groupnorm_silu_forward", x.device, x, act, gw, gb, N, H * W, Cin, groups, float(eps), 1, ws, mr)
+        if part is None:
+            return _conv_launch(act, w, bias, residual, Cout), mr, None
+        y = _tiled_launch(_conv_route(N, H, W, Cin, Cout) or "patch", act, w, bias, residual, Cout, part)
+    mr_next = None
+    if part is not None:
+        g2, eps2 = next_norm
+        mr_next = torch.empty(N * g2 * 2, dtype=torch.float32, device=x.device)
+        launch("gd_nn_groupnorm_finish_partials", x.device, part, N, rows, Cout, g2, H * W, float(eps2), mr_next)
     return y, mr, mr_next
 
 
@@ -1107,9 +1035,7 @@ class _ResnetBlockFrozen(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dmr=None):
         x, h, mr1, mr2, n1w, n1b, n2w, n2b = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _grad_nhwc_bf16(dy)
         dact2 = _conv_launch(dy, _flipped(ctx.c2w), None, None, ctx.c2w.shape[1])
         dh = _gn_bwd_launch(h, dact2, n2w, n2b, mr2, ctx.groups, True)
         dact1 = _conv_launch(dh, _flipped(ctx.c1w), None, None, ctx.c1w.shape[1])
@@ -1158,27 +1084,24 @@ def resnet_block_frozen(x, block, next_norm=None):
 def _up2_weights(weight):
     """Pre-summed filters of the upsample-fused convolution (include/gd_nn.h, gd_nn_conv3x3_up2_forward): two
     [Cout, Cin, 3, 3] channels_last tensors (even / odd output rows), summed in fp32, cached on the weight."""
-    key = (weight.data_ptr(), weight._version)
-    cached = getattr(weight, "_gd_up2", None)
-    if cached is not None and cached[0] == key:
-        return cached[1], cached[2]
-    w = weight.detach().float()
-    rows = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}
-    out = []
-    for py in (0, 1):
-        slots = torch.zeros((weight.shape[0], weight.shape[1], 9), dtype=torch.float32, device=weight.device)
-        for px in (0, 1):
-            for ty in (0, 1):
-                for tx in (0, 1):
-                    acc = 0
-                    for ky in rows[(py, ty)]:
-                        for kx in rows[(px, tx)]:
-                            acc = acc + w[:, :, ky, kx]
-                    slots[:, :, px * 4 + ty * 2 + tx] = acc
-        out.append(slots.view(weight.shape[0], weight.shape[1], 3, 3).to(torch.bfloat16)
-                   .contiguous(memory_format=torch.channels_last))
-    weight._gd_up2 = (key, out[0], out[1])
-    return out[0], out[1]
+    def build():
+        w = weight.detach().float()
+        rows = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}
+        out = []
+        for py in (0, 1):
+            slots = torch.zeros((weight.shape[0], weight.shape[1], 9), dtype=torch.float32, device=weight.device)
+            for px in (0, 1):
+                for ty in (0, 1):
+                    for tx in (0, 1):
+                        acc = 0
+                        for ky in rows[(py, ty)]:
+                            for kx in rows[(px, tx)]:
+                                acc = acc + w[:, :, ky, kx]
+                        slots[:, :, px * 4 + ty * 2 + tx] = acc
+            out.append(slots.view(weight.shape[0], weight.shape[1], 3, 3).to(torch.bfloat16)
+                       .contiguous(memory_format=torch.channels_last))
+        return out[0], out[1]
+    return _derived(weight, "_gd_up2", build)
 
 
 def upsample2x_conv3x3_supported(x, weight) -> bool:
@@ -1199,13 +1122,8 @@ def upsample2x_conv3x3(x, weight, bias=None):
     Cout = weight.shape[0]
     we, wo = _up2_weights(weight)
     y = torch.empty((N, Cout, 2 * H, 2 * W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_conv3x3_up2_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), we.data_ptr(),
-                                          wo.data_ptr(), None if bias is None else bias.contiguous().data_ptr(),
-                                          y.data_ptr(), N, H, W, Cin, Cout)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_conv3x3_up2_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+    launch("gd_nn_conv3x3_up2_forward", x.device, x, we, wo, None if bias is None else bias.contiguous(), y, N, H, W, Cin,
+           Cout)
     return y
 
 
@@ -1219,16 +1137,9 @@ class _Conv3x3S2(torch.autograd.Function):
         Cout = weight.shape[0]
         Ho, Wo = (H + pad_lo - 2) // 2 + 1, (W + pad_lo - 2) // 2 + 1
         y = torch.empty((N, Cout, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        L = lib()
-        ws_bytes = L.gd_nn_conv3x3_s2_ws_bytes(N, H, W, Cin, Cout, pad_lo, 0)     # small maps: split-K scratch
+        ws_bytes = lib().gd_nn_conv3x3_s2_ws_bytes(N, H, W, Cin, Cout, pad_lo, 0)     # small maps: split-K scratch
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-        with torch.cuda.device(x.device):
-            ret = L.gd_nn_conv3x3_s2_forward_ws(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-                                                weight.data_ptr(), None if bias is None else bias.data_ptr(),
-                                                y.data_ptr(), N, H, W, Cin, Cout, pad_lo,
-                                                None if ws is None else ws.data_ptr(), ws_bytes)
-        if ret < 0:
-            raise RuntimeError(f"gd_nn_conv3x3_s2_forward failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+        launch("gd_nn_conv3x3_s2_forward_ws", x.device, x, weight, bias, y, N, H, W, Cin, Cout, pad_lo, ws, ws_bytes)
         ctx.weight, ctx.pad_lo, ctx.in_shape = weight, pad_lo, (N, Cin, H, W)
         return y
 
@@ -1236,20 +1147,12 @@ class _Conv3x3S2(torch.autograd.Function):
     def backward(ctx, dy):
         N, Cin, H, W = ctx.in_shape
         Cout = ctx.weight.shape[0]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        dy = _grad_nhwc_bf16(dy)
         dx = torch.empty((N, Cin, H, W), dtype=torch.bfloat16, device=dy.device, memory_format=torch.channels_last)
         wf = _flipped(ctx.weight)
-        L = lib()
-        ws_bytes = L.gd_nn_conv3x3_s2_ws_bytes(N, H, W, Cin, Cout, ctx.pad_lo, 1)
+        ws_bytes = lib().gd_nn_conv3x3_s2_ws_bytes(N, H, W, Cin, Cout, ctx.pad_lo, 1)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device) if ws_bytes else None
-        with torch.cuda.device(dy.device):
-            ret = L.gd_nn_conv3x3_s2_dgrad_ws(torch.cuda.current_stream(dy.device).cuda_stream, dy.data_ptr(),
-                                              wf.data_ptr(), dx.data_ptr(), N, H, W, Cin, Cout, ctx.pad_lo,
-                                              None if ws is None else ws.data_ptr(), ws_bytes)
-        if ret < 0:
-            raise RuntimeError(f"gd_nn_conv3x3_s2_dgrad failed ({ret}): {L.gd_nn_conv_last_error().decode()}")
+        launch("gd_nn_conv3x3_s2_dgrad_ws", dy.device, dy, wf, dx, N, H, W, Cin, Cout, ctx.pad_lo, ws, ws_bytes)
         return dx, None, None, None
 
 
@@ -1284,12 +1187,7 @@ def _rowwise_ok(*ts):
 def _geglu_fwd(x, inner):
     x = x.contiguous()
     y = torch.empty(x.shape[:-1] + (inner,), dtype=x.dtype, device=x.device)
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_geglu_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), y.data_ptr(),
-                                    x.numel() // (2 * inner), inner)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_geglu_forward failed ({ret}): {L.gd_nn_elementwise_last_error().decode()}")
+    launch("gd_nn_geglu_forward", x.device, x, y, x.numel() // (2 * inner), inner)
     return x, y
 
 
@@ -1310,34 +1208,21 @@ class _GegluTrain(torch.autograd.Function):
         inner = x.shape[-1] // 2
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        L = lib()
-        with torch.cuda.device(x.device):
-            ret = L.gd_nn_geglu_backward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), dy.data_ptr(),
-                                         dx.data_ptr(), x.numel() // (2 * inner), inner)
-        if ret < 0:
-            raise RuntimeError(f"gd_nn_geglu_backward failed ({ret}): {L.gd_nn_elementwise_last_error().decode()}")
+        launch("gd_nn_geglu_backward", x.device, x, dy, dx, x.numel() // (2 * inner), inner)
         return dx
 
 
 def softmax_rows_(s):
     """In-place softmax over the last dimension of a contiguous bf16 GPU tensor (gd_nn_softmax_rows_forward)."""
     L = s.shape[-1]
-    with torch.cuda.device(s.device):
-        ret = lib().gd_nn_softmax_rows_forward(torch.cuda.current_stream(s.device).cuda_stream, s.data_ptr(), s.data_ptr(),
-                                               s.numel() // L, L)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_softmax_rows_forward failed ({ret}): {lib().gd_nn_elementwise_last_error().decode()}")
+    launch("gd_nn_softmax_rows_forward", s.device, s, s, s.numel() // L, L)
     return s
 
 
 def softmax_rows_backward_(p, dp):
     """``dp <- p * (dp - sum(p * dp, -1))`` in place (gd_nn_softmax_rows_backward): the gradient of the scores."""
     L = p.shape[-1]
-    with torch.cuda.device(p.device):
-        ret = lib().gd_nn_softmax_rows_backward(torch.cuda.current_stream(p.device).cuda_stream, p.data_ptr(), dp.data_ptr(),
-                                                dp.data_ptr(), p.numel() // L, L)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_softmax_rows_backward failed ({ret}): {lib().gd_nn_elementwise_last_error().decode()}")
+    launch("gd_nn_softmax_rows_backward", p.device, p, dp, dp, p.numel() // L, L)
     return dp
 
 
@@ -1384,12 +1269,7 @@ def single_head_attention(qkv):
 def _conv1x1_c8_launch(x, weight, bias, transposed):
     """x: [B, 8, H, W] bf16 in channels_last memory (NHWC) -> the same shape and layout."""
     y = torch.empty_like(x, memory_format=torch.channels_last)
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_conv1x1_c8(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), weight.data_ptr(),
-                                 None if bias is None else bias.data_ptr(), y.data_ptr(), x.numel() // 8, int(transposed))
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_conv1x1_c8 failed ({ret}): {L.gd_nn_elementwise_last_error().decode()}")
+    launch("gd_nn_conv1x1_c8", x.device, x, weight, bias, y, x.numel() // 8, int(transposed))
     return y
 
 
@@ -1448,13 +1328,7 @@ def geglu(x):
 def _ln_backward(s, dy, weight, ds, eps):
     Cc = s.shape[-1]
     dx = torch.empty_like(s)
-    L = lib()
-    with torch.cuda.device(s.device):
-        ret = L.gd_nn_layernorm_backward(torch.cuda.current_stream(s.device).cuda_stream, s.data_ptr(), dy.data_ptr(),
-                                         weight.data_ptr(), None if ds is None else ds.data_ptr(), dx.data_ptr(),
-                                         s.numel() // Cc, Cc, float(eps))
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_layernorm_backward failed ({ret}): {L.gd_nn_elementwise_last_error().decode()}")
+    launch("gd_nn_layernorm_backward", s.device, s, dy, weight, ds, dx, s.numel() // Cc, Cc, float(eps))
     return dx
 
 
@@ -1466,18 +1340,11 @@ def _add_ln_fwd(x, residual, weight, bias, eps, want_sum):
     like = x if residual is None else residual      # (x may hold a divisor of the residual's rows: read at row % x_rows)
     s = torch.empty_like(like) if (residual is not None and want_sum) else None
     y = torch.empty_like(like)
-    L = lib()
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        res_p, s_p = None if residual is None else residual.data_ptr(), None if s is None else s.data_ptr()
-        if like.numel() == x.numel():
-            ret = L.gd_nn_add_layernorm_forward(stream, x.data_ptr(), res_p, weight.data_ptr(), bias.data_ptr(), float(eps), s_p,
-                                                y.data_ptr(), x.numel() // Cc, Cc)
-        else:
-            ret = L.gd_nn_add_layernorm_forward_bcast(stream, x.data_ptr(), res_p, weight.data_ptr(), bias.data_ptr(), float(eps),
-                                                      s_p, y.data_ptr(), like.numel() // Cc, Cc, x.numel() // Cc)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_add_layernorm_forward failed ({ret}): {L.gd_nn_elementwise_last_error().decode()}")
+    if like.numel() == x.numel():
+        launch("gd_nn_add_layernorm_forward", x.device, x, residual, weight, bias, float(eps), s, y, x.numel() // Cc, Cc)
+    else:
+        launch("gd_nn_add_layernorm_forward_bcast", x.device, x, residual, weight, bias, float(eps), s, y, like.numel() // Cc,
+               Cc, x.numel() // Cc)
     return (x if residual is None else s), y
 
 
@@ -1558,13 +1425,8 @@ def attention_d64(q, k, v):
     L = lib()
     o = torch.empty((B, S, H * 64), dtype=torch.bfloat16, device=q.device)
     ws = torch.empty(L.gd_nn_attention_ws_bytes(B, Skv, H), dtype=torch.uint8, device=q.device)
-    with torch.cuda.device(q.device):
-        ret = L.gd_nn_attention_d64_forward(torch.cuda.current_stream(q.device).cuda_stream, q.data_ptr(), k.data_ptr(),
-                                            v.data_ptr(), o.data_ptr(), ws.data_ptr(), B, S, Skv, H, q.stride(0), q.stride(1),
-                                            k.stride(0), k.stride(1), v.stride(0), v.stride(1), o.stride(0), o.stride(1),
-                                            64 ** -0.5, kv_len)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_attention_d64_forward failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
+    launch("gd_nn_attention_d64_forward", q.device, q, k, v, o, ws, B, S, Skv, H, q.stride(0), q.stride(1), k.stride(0),
+           k.stride(1), v.stride(0), v.stride(1), o.stride(0), o.stride(1), 64 ** -0.5, kv_len)
     return o
 
 
@@ -1582,13 +1444,8 @@ class _AttentionD64Train(torch.autograd.Function):
         o = torch.empty((B, S, H * 64), dtype=torch.bfloat16, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         ws = torch.empty(L.gd_nn_attention_ws_bytes(B, Skv, H), dtype=torch.uint8, device=q.device)
-        with torch.cuda.device(q.device):
-            ret = L.gd_nn_attention_d64_forward_lse(torch.cuda.current_stream(q.device).cuda_stream, q.data_ptr(), k.data_ptr(),
-                                                    v.data_ptr(), o.data_ptr(), lse.data_ptr(), ws.data_ptr(), B, S, Skv, H,
-                                                    q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
-                                                    o.stride(0), o.stride(1), 64 ** -0.5, kv_len)
-        if ret < 0:
-            raise RuntimeError(f"gd_nn_attention_d64_forward_lse failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
+        launch("gd_nn_attention_d64_forward_lse", q.device, q, k, v, o, lse, ws, B, S, Skv, H, q.stride(0), q.stride(1),
+               k.stride(0), k.stride(1), v.stride(0), v.stride(1), o.stride(0), o.stride(1), 64 ** -0.5, kv_len)
         ctx.save_for_backward(q, k, v, o, lse)
         return o
 
@@ -1607,15 +1464,10 @@ class _AttentionD64Train(torch.autograd.Function):
             dk = torch.empty((B, kv_len, H, 64), dtype=torch.bfloat16, device=q.device)
             dv = torch.empty((B, kv_len, H, 64), dtype=torch.bfloat16, device=q.device)
             ws = torch.empty(L.gd_nn_attention_bwd_ws_bytes(B, S, Skv, H), dtype=torch.uint8, device=q.device)
-            with torch.cuda.device(q.device):
-                ret = L.gd_nn_attention_d64_backward(
-                    torch.cuda.current_stream(q.device).cuda_stream, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                    do.data_ptr(), lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), ws.data_ptr(), B, S, Skv, H,
-                    q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), o.stride(0), o.stride(1),
-                    do.stride(0), do.stride(1), dq.stride(0), dq.stride(1), dk.stride(0), dk.stride(1), dv.stride(0),
-                    dv.stride(1), 64 ** -0.5, kv_len)
-            if ret < 0:
-                raise RuntimeError(f"gd_nn_attention_d64_backward failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
+            launch("gd_nn_attention_d64_backward", q.device, q, k, v, o, do, lse, dq, dk, dv, ws, B, S, Skv, H,
+                   q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), o.stride(0), o.stride(1),
+                   do.stride(0), do.stride(1), dq.stride(0), dq.stride(1), dk.stride(0), dk.stride(1), dv.stride(0),
+                   dv.stride(1), 64 ** -0.5, kv_len)
             return dq, dk, dv
         z = torch.zeros((), dtype=torch.long, device=q.device)       # philox seed / offset: unused without dropout
         dq, dk, dv = torch.ops.aten._scaled_dot_product_flash_attention_backward(
@@ -1634,14 +1486,9 @@ def attention_d64_vt(q, k, vt):
     B, S, H, _ = q.shape
     Skv = k.shape[1]
     assert vt.shape == (B, H * 64, Skv) and vt.is_contiguous() and vt.dtype == torch.bfloat16 and Skv % 64 == 0
-    L = lib()
     o = torch.empty((B, S, H * 64), dtype=torch.bfloat16, device=q.device)
-    with torch.cuda.device(q.device):
-        ret = L.gd_nn_attention_d64_forward_vt(torch.cuda.current_stream(q.device).cuda_stream, q.data_ptr(), k.data_ptr(),
-                                               vt.data_ptr(), o.data_ptr(), B, S, Skv, H, q.stride(0), q.stride(1),
-                                               k.stride(0), k.stride(1), o.stride(0), o.stride(1), 64 ** -0.5)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_attention_d64_forward_vt failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
+    launch("gd_nn_attention_d64_forward_vt", q.device, q, k, vt, o, B, S, Skv, H, q.stride(0), q.stride(1), k.stride(0),
+           k.stride(1), o.stride(0), o.stride(1), 64 ** -0.5)
     return o
 
 
@@ -1654,17 +1501,11 @@ def attention_d64_vt_strided(q, k, vt, kv_len: int):
     B, Skv = vt.shape[0], vt.shape[2]
     assert vt.shape[1] == H * 64 and vt.stride(2) == 1 and vt.stride(1) == Skv and vt.dtype == torch.bfloat16 and Skv % 64 == 0
     assert k.shape[0] == B and B % Bq == 0
-    L = lib()
     o = torch.empty((B, S, H * 64), dtype=torch.bfloat16, device=q.device)
-    with torch.cuda.device(q.device):
-        stream = torch.cuda.current_stream(q.device).cuda_stream
-        for r in range(0, B, Bq):
-            ret = L.gd_nn_attention_d64_forward_vt_strided(stream, q.data_ptr(), k[r:r + Bq].data_ptr(), vt[r:r + Bq].data_ptr(),
-                                                           o[r:r + Bq].data_ptr(), Bq, S, Skv, H, q.stride(0), q.stride(1),
-                                                           k.stride(0), k.stride(1), vt.stride(0), o.stride(0), o.stride(1),
-                                                           64 ** -0.5, int(kv_len))
-            if ret < 0:
-                raise RuntimeError(f"gd_nn_attention_d64_forward_vt_strided failed ({ret}): {L.gd_nn_attention_last_error().decode()}")
+    for r in range(0, B, Bq):
+        launch("gd_nn_attention_d64_forward_vt_strided", q.device, q, k[r:r + Bq], vt[r:r + Bq], o[r:r + Bq], Bq, S, Skv, H,
+               q.stride(0), q.stride(1), k.stride(0), k.stride(1), vt.stride(0), o.stride(0), o.stride(1), 64 ** -0.5,
+               int(kv_len))
     return o
 
 
@@ -1679,10 +1520,7 @@ class _VaePrologue(torch.autograd.Function):
     def forward(ctx, x, OH, OW):
         N, Cc, H, W = x.shape
         y = torch.empty((N, 3, OH, OW), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        L = lib()
-        with torch.cuda.device(x.device):
-            _check(L.gd_nn_vae_prologue_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), y.data_ptr(),
-                                                N, H, W, OH, OW), "gd_nn_vae_prologue_forward", "gd_nn_prologue_last_error")
+        launch("gd_nn_vae_prologue_forward", x.device, x, y, N, H, W, OH, OW)
         ctx.shape = (N, H, W, OH, OW)
         return y
 
@@ -1702,10 +1540,7 @@ class _VaePrologue(torch.autograd.Function):
         else:
             src, CG = dy.contiguous(memory_format=torch.channels_last), 3
         dx = torch.empty((N, 3, H, W), dtype=torch.float32, device=dy.device)
-        L = lib()
-        with torch.cuda.device(dy.device):
-            _check(L.gd_nn_vae_prologue_backward(torch.cuda.current_stream(dy.device).cuda_stream, src.data_ptr(),
-                                                 dx.data_ptr(), N, H, W, OH, OW, CG), "gd_nn_vae_prologue_backward", "gd_nn_prologue_last_error")
+        launch("gd_nn_vae_prologue_backward", dy.device, src, dx, N, H, W, OH, OW, CG)
         return dx, None, None
 
 
@@ -1754,13 +1589,9 @@ def vae_decode_stem(latents, inv_scale: float, pq_weight, pq_bias, weight, bias)
         Cout = weight.shape[0]
         wc = weight.contiguous(memory_format=torch.channels_last)
         y = torch.empty((N, Cout, h, w), dtype=torch.bfloat16, device=lat.device, memory_format=torch.channels_last)
-        with torch.cuda.device(lat.device):
-            _check(lib().gd_nn_vae_decoder_stem(torch.cuda.current_stream(lat.device).cuda_stream, lat.data_ptr(),
-                                                int(lat.dtype == torch.bfloat16), float(inv_scale),
-                                                pq_weight.contiguous().data_ptr(),
-                                                None if pq_bias is None else pq_bias.contiguous().data_ptr(), wc.data_ptr(),
-                                                None if bias is None else bias.contiguous().data_ptr(), y.data_ptr(), N, h, w,
-                                                Cout), "gd_nn_vae_decoder_stem", "gd_nn_vae_decoder_last_error")
+        launch("gd_nn_vae_decoder_stem", lat.device, lat, int(lat.dtype == torch.bfloat16), float(inv_scale),
+               pq_weight.contiguous(), None if pq_bias is None else pq_bias.contiguous(), wc,
+               None if bias is None else bias.contiguous(), y, N, h, w, Cout)
         return y
     _note_fallback("vae_decode_stem", weight, "needs [N, 4, h, w] fp32/bf16 GPU latents, frozen bf16 weights, Cout % 64 == 0 <= 512")
     z = (latents * inv_scale).to(weight.dtype)
@@ -1788,23 +1619,17 @@ def vae_decode_head(x, norm_weight, norm_bias, groups: int, eps: float, weight, 
     if vae_decode_head_supported(x, norm_weight, norm_bias, groups, weight, bias):
         x = x.contiguous(memory_format=torch.channels_last)
         N, C, H, W = x.shape
-        L = lib()
         out = torch.empty((N, 3, H, W), dtype=torch.bfloat16 if m == VAE_HEAD_RAW else torch.float32, device=x.device,
                           memory_format=torch.channels_last)
         wc = weight.contiguous(memory_format=torch.channels_last)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            if mean_rstd is None:
-                mean_rstd = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
-                _check(L.gd_nn_groupnorm_stats(stream, x.data_ptr(), N, H * W, C, groups, float(eps),
-                                               _gn_workspace(x, N, groups).data_ptr(), mean_rstd.data_ptr()),
-                       "gd_nn_groupnorm_stats")
-            elif mean_rstd.dtype != torch.float32 or mean_rstd.numel() != N * groups * 2 or not mean_rstd.is_contiguous():
-                raise ValueError("vae_decode_head: mean_rstd must be contiguous fp32 [N * groups * 2]")
-            _check(L.gd_nn_vae_decoder_head(stream, x.data_ptr(), mean_rstd.data_ptr(), norm_weight.contiguous().data_ptr(),
-                                            norm_bias.contiguous().data_ptr(), int(groups), wc.data_ptr(),
-                                            None if bias is None else bias.contiguous().data_ptr(), out.data_ptr(), m, N, H,
-                                            W, C), "gd_nn_vae_decoder_head", "gd_nn_vae_decoder_last_error")
+        if mean_rstd is None:
+            mean_rstd = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
+            launch("gd_nn_groupnorm_stats", x.device, x, N, H * W, C, groups, float(eps), _gn_workspace(x, N, groups),
+                   mean_rstd)
+        elif mean_rstd.dtype != torch.float32 or mean_rstd.numel() != N * groups * 2 or not mean_rstd.is_contiguous():
+            raise ValueError("vae_decode_head: mean_rstd must be contiguous fp32 [N * groups * 2]")
+        launch("gd_nn_vae_decoder_head", x.device, x, mean_rstd, norm_weight.contiguous(), norm_bias.contiguous(),
+               int(groups), wc, None if bias is None else bias.contiguous(), out, m, N, H, W, C)
         return out
     _note_fallback("vae_decode_head", x, "needs bf16 GPU activations with C % 64 == 0 <= 256 and frozen bf16 C -> 3 weights")
     r = F.conv2d(F.silu(F.group_norm(x, groups, norm_weight, norm_bias, eps)), weight, bias, padding=1)
@@ -1823,10 +1648,7 @@ class _SparsityHead(torch.autograd.Function):
         m = dmax.detach().reshape(1).to(torch.float32)
         sums = torch.empty(2, dtype=torch.float64, device=d.device)
         n = d.numel()
-        L = lib()
-        with torch.cuda.device(d.device):
-            _check(L.gd_nn_sparsity_forward(torch.cuda.current_stream(d.device).cuda_stream, d.data_ptr(), m.data_ptr(), n,
-                                            sums.data_ptr()), "gd_nn_sparsity_forward", "gd_nn_prologue_last_error")
+        launch("gd_nn_sparsity_forward", d.device, d, m, n, sums)
         ctx.save_for_backward(d, m, sums)
         return (sums[0] / n).to(torch.float32)
 
@@ -1836,10 +1658,7 @@ class _SparsityHead(torch.autograd.Function):
         n = d.numel()
         g32 = g.reshape(1).to(torch.float32).contiguous()
         dd = torch.empty_like(d)
-        L = lib()
-        with torch.cuda.device(d.device):
-            _check(L.gd_nn_sparsity_backward(torch.cuda.current_stream(d.device).cuda_stream, d.data_ptr(), m.data_ptr(),
-                                             g32.data_ptr(), n, dd.data_ptr()), "gd_nn_sparsity_backward", "gd_nn_prologue_last_error")
+        launch("gd_nn_sparsity_backward", d.device, d, m, g32, n, dd)
         dmax_grad = (-(sums[1] / n).to(torch.float32) / (m[0] + 1e-5)) * g32[0]
         return dd, dmax_grad.reshape(())
 
@@ -1847,11 +1666,6 @@ class _SparsityHead(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 # rank-4 LoRA branch (csrc/nn_lora.hip): y = base + scale * up(down(x)), forward and backward, fp32 accumulation
 # ---------------------------------------------------------------------------------------------------------------------
-def _lora_check(ret, what):
-    if ret < 0:
-        raise RuntimeError(f"{what} failed ({ret}): {lib().gd_nn_lora_last_error().decode()}")
-
-
 def lora_branch_supported(x, base, down_w, up_w) -> bool:
     return (x.is_cuda and x.dtype == torch.bfloat16 and base.dtype == torch.bfloat16 and down_w.dtype == torch.float32
             and up_w.dtype == torch.float32 and down_w.shape[0] == 4 and up_w.shape[1] == 4 and x.shape[-1] % 8 == 0
@@ -1861,31 +1675,22 @@ def lora_branch_supported(x, base, down_w, up_w) -> bool:
 def _lora_rowdot(a2d, w, scale, w_is_k_by_4):
     M, K = a2d.shape
     h = torch.empty((M, 4), dtype=torch.float32, device=a2d.device)
-    with torch.cuda.device(a2d.device):
-        _lora_check(lib().gd_nn_lora_rowdot(torch.cuda.current_stream(a2d.device).cuda_stream, a2d.data_ptr(), w.data_ptr(),
-                                            h.data_ptr(), M, K, float(scale), int(w_is_k_by_4)), "gd_nn_lora_rowdot")
+    launch("gd_nn_lora_rowdot", a2d.device, a2d, w, h, M, K, float(scale), int(w_is_k_by_4))
     return h
 
 
 def _lora_rank4_add(h, w, base2d, N, w_is_n_by_4):
     M = h.shape[0]
     y = torch.empty((M, N), dtype=torch.bfloat16, device=h.device)
-    with torch.cuda.device(h.device):
-        _lora_check(lib().gd_nn_lora_rank4_add(torch.cuda.current_stream(h.device).cuda_stream, h.data_ptr(), w.data_ptr(),
-                                               None if base2d is None else base2d.data_ptr(), y.data_ptr(), M, N,
-                                               int(w_is_n_by_4)), "gd_nn_lora_rank4_add")
+    launch("gd_nn_lora_rank4_add", h.device, h, w, base2d, y, M, N, int(w_is_n_by_4))
     return y
 
 
 def _lora_colreduce(a2d, v, scale, g_is_j_by_4):
     M, J = a2d.shape
-    L = lib()
-    scratch = torch.empty(L.gd_nn_lora_colreduce_scratch_floats(M, J), dtype=torch.float32, device=a2d.device)
+    scratch = torch.empty(lib().gd_nn_lora_colreduce_scratch_floats(M, J), dtype=torch.float32, device=a2d.device)
     g = torch.empty((J, 4) if g_is_j_by_4 else (4, J), dtype=torch.float32, device=a2d.device)
-    with torch.cuda.device(a2d.device):
-        _lora_check(L.gd_nn_lora_colreduce(torch.cuda.current_stream(a2d.device).cuda_stream, a2d.data_ptr(), v.data_ptr(),
-                                           scratch.data_ptr(), g.data_ptr(), M, J, float(scale), int(g_is_j_by_4)),
-                    "gd_nn_lora_colreduce")
+    launch("gd_nn_lora_colreduce", a2d.device, a2d, v, scratch, g, M, J, float(scale), int(g_is_j_by_4))
     return g
 
 
@@ -1900,11 +1705,7 @@ def _lora_row_fused(a2d, w1, w2, base2d, N, scale, backward, want_h=True):
         return _lora_rank4_add(h, w2, base2d, N, int(not backward)), (h if want_h else None)
     h = torch.empty((M, 4), dtype=torch.float32, device=a2d.device) if want_h else None
     y = torch.empty((M, N), dtype=torch.bfloat16, device=a2d.device)
-    with torch.cuda.device(a2d.device):
-        _lora_check(lib().gd_nn_lora_row_fused(torch.cuda.current_stream(a2d.device).cuda_stream, a2d.data_ptr(), w1.data_ptr(),
-                                               w2.data_ptr(), None if base2d is None else base2d.data_ptr(),
-                                               None if h is None else h.data_ptr(), y.data_ptr(), M, K, N, float(scale),
-                                               int(backward)), "gd_nn_lora_row_fused")
+    launch("gd_nn_lora_row_fused", a2d.device, a2d, w1, w2, base2d, h, y, M, K, N, float(scale), int(backward))
     return y, h
 
 
@@ -1933,9 +1734,9 @@ class LoraGradGroup:
         eb = L.gd_nn_lora_colreduce_group_entry_bytes()
         buf = (C.c_ubyte * eb)()
         g3 = (C.c_int * 3)()
-        _lora_check(L.gd_nn_lora_colreduce_group_desc(buf, dy.data_ptr(), hs.data_ptr(), x2d.data_ptr(), dh.data_ptr(),
-                                                      scratch.data_ptr(), sink_up.data_ptr(), sink_down.data_ptr(), M, N, K, 1, g3),
-                    "gd_nn_lora_colreduce_group_desc")
+        _check(L.gd_nn_lora_colreduce_group_desc(buf, dy.data_ptr(), hs.data_ptr(), x2d.data_ptr(), dh.data_ptr(),
+                                                 scratch.data_ptr(), sink_up.data_ptr(), sink_down.data_ptr(), M, N, K, 1, g3),
+               "gd_nn_lora_colreduce_group_desc")       # (takes no stream: a plain call)
         if not self.entries:
             _LORA_GROUPS_OPEN.append(weakref.ref(self))
         self.entries.append(bytes(buf))
@@ -1949,11 +1750,7 @@ class LoraGradGroup:
             return
         n = len(self.entries)
         table = (C.c_ubyte * (n * len(self.entries[0]))).from_buffer_copy(b"".join(self.entries))
-        L = lib()
-        with torch.cuda.device(device):
-            _lora_check(L.gd_nn_lora_colreduce_group_launch(torch.cuda.current_stream(device).cuda_stream, table, n,
-                                                            self.grid[0], self.grid[1], self.grid[2]),
-                        "gd_nn_lora_colreduce_group_launch")
+        launch("gd_nn_lora_colreduce_group_launch", device, table, n, self.grid[0], self.grid[1], self.grid[2])
         self.entries, self.keep, self.grid = [], [], [0, 0, 0]
         self.launches += 1
 
@@ -2027,18 +1824,11 @@ def _lora_backward(ctx, dy, dx_base, need_x, need_down, need_up):
             if grp is not None:            # ... and nobody reads them before the optimizer step: one grouped launch at the end
                 grp.add(dy, hs, x2d, dh, scratch, sink_up, sink_down, M, N, K)
                 return dx, None, None
-            with torch.cuda.device(dy.device):
-                _lora_check(L.gd_nn_lora_colreduce_pair_into(torch.cuda.current_stream(dy.device).cuda_stream, dy.data_ptr(),
-                                                             hs.data_ptr(), x2d.data_ptr(), dh.data_ptr(), scratch.data_ptr(),
-                                                             sink_up.data_ptr(), sink_down.data_ptr(), M, N, K, 1),
-                            "gd_nn_lora_colreduce_pair_into")
+            launch("gd_nn_lora_colreduce_pair_into", dy.device, dy, hs, x2d, dh, scratch, sink_up, sink_down, M, N, K, 1)
             return dx, None, None
         d_up = torch.empty((N, 4), dtype=torch.float32, device=dy.device)
         d_down = torch.empty((4, K), dtype=torch.float32, device=dy.device)
-        with torch.cuda.device(dy.device):
-            _lora_check(L.gd_nn_lora_colreduce_pair(torch.cuda.current_stream(dy.device).cuda_stream, dy.data_ptr(), hs.data_ptr(),
-                                                    x2d.data_ptr(), dh.data_ptr(), scratch.data_ptr(), d_up.data_ptr(),
-                                                    d_down.data_ptr(), M, N, K), "gd_nn_lora_colreduce_pair")
+        launch("gd_nn_lora_colreduce_pair", dy.device, dy, hs, x2d, dh, scratch, d_up, d_down, M, N, K)
     elif need_up:
         d_up = _lora_colreduce(dy, hs, 1.0, 1)                         # [N, 4]: sum_m dy[m, n] * scale * h[m, r]
     elif need_down:
@@ -2129,18 +1919,11 @@ def sparsity_loss(depth, dmax):
 FP8_MAX = 448.0
 
 
-def _check8(ret, what):
-    if ret < 0:
-        raise RuntimeError(f"{what} failed ({ret}): {lib().gd_nn_fp8_last_error().decode()}")
-
-
 def fp8_quantize(x, scale: float):
     """bf16 tensor -> e4m3 bytes (uint8 tensor of the same shape), value = scale * byte."""
     xc = x.contiguous()
     y = torch.empty(xc.shape, dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _check8(lib().gd_nn_fp8_quantize(torch.cuda.current_stream(x.device).cuda_stream, xc.data_ptr(), y.data_ptr(),
-                                         xc.numel(), 1.0 / scale), "gd_nn_fp8_quantize")
+    launch("gd_nn_fp8_quantize", x.device, xc, y, xc.numel(), 1.0 / scale)
     return y
 
 
@@ -2150,9 +1933,7 @@ def fp8_pack_weights(w2d, scale: float):
     Kp = (K + 127) // 128 * 128
     wc = w2d.contiguous()
     out = torch.empty((rows, Kp), dtype=torch.uint8, device=w2d.device)
-    with torch.cuda.device(w2d.device):
-        _check8(lib().gd_nn_fp8_pack_weights(torch.cuda.current_stream(w2d.device).cuda_stream, wc.data_ptr(),
-                                             out.data_ptr(), rows, K, Kp, 1.0 / scale), "gd_nn_fp8_pack_weights")
+    launch("gd_nn_fp8_pack_weights", w2d.device, wc, out, rows, K, Kp, 1.0 / scale)
     return out
 
 
@@ -2161,11 +1942,7 @@ def fp8_linear(x8, w8, bias, residual, K: int, dq: float):
     Nout, Kp = w8.shape
     M = x8.numel() // K
     y = torch.empty(x8.shape[:-1] + (Nout,), dtype=torch.bfloat16, device=x8.device)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    with torch.cuda.device(x8.device):
-        _check8(lib().gd_nn_fp8_linear_forward(torch.cuda.current_stream(x8.device).cuda_stream, x8.data_ptr(), w8.data_ptr(),
-                                               p(bias), p(residual), y.data_ptr(), M, K, Kp, Nout, dq),
-                "gd_nn_fp8_linear_forward")
+    launch("gd_nn_fp8_linear_forward", x8.device, x8, w8, bias, residual, y, M, K, Kp, Nout, dq)
     return y
 
 
@@ -2177,11 +1954,7 @@ def fp8_conv3x3(x8, w8, bias, residual, Cin: int, dq: float):
     Cout = w8.shape[0] // 9
     y = torch.empty((N, Cout, H, W), dtype=torch.bfloat16, device=x8.device, memory_format=torch.channels_last)
     b, bs = _bias_and_stride(bias)
-    with torch.cuda.device(x8.device):
-        _check8(lib().gd_nn_fp8_conv3x3_forward(torch.cuda.current_stream(x8.device).cuda_stream, x8.data_ptr(),
-                                                w8.data_ptr(), None if b is None else b.data_ptr(), bs,
-                                                None if residual is None else residual.data_ptr(), y.data_ptr(), N, H, W,
-                                                Cin, CinP, Cout, dq), "gd_nn_fp8_conv3x3_forward")
+    launch("gd_nn_fp8_conv3x3_forward", x8.device, x8, w8, b, bs, residual, y, N, H, W, Cin, CinP, Cout, dq)
     return y
 
 
@@ -2194,11 +1967,8 @@ def group_norm_silu_fp8(x, weight, bias, groups: int, eps: float, silu: bool, sc
     ws = _gn_workspace(x, N, groups)
     mr = torch.empty(N * groups * 2, dtype=torch.float32, device=x.device)
     w, b = weight.contiguous(), bias.contiguous()
-    with torch.cuda.device(x.device):
-        _check(lib().gd_nn_groupnorm_silu_forward_fp8(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-                                                      y.data_ptr(), w.data_ptr(), b.data_ptr(), N, H * W, Cc, groups,
-                                                      float(eps), int(silu), ws.data_ptr(), mr.data_ptr(), 1.0 / scale),
-               "gd_nn_groupnorm_silu_forward_fp8")
+    launch("gd_nn_groupnorm_silu_forward_fp8", x.device, x, y, w, b, N, H * W, Cc, groups, float(eps), int(silu), ws, mr,
+           1.0 / scale)
     return y
 
 
@@ -2266,12 +2036,7 @@ def linear_320(x, weight, bias=None):
     inference only."""
     M, N = x.numel() // 320, weight.shape[0]
     y = torch.empty(x.shape[:-1] + (N,), dtype=torch.bfloat16, device=x.device)
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_linear_k320_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), weight.data_ptr(),
-                                          None if bias is None else bias.data_ptr(), y.data_ptr(), M, N)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_linear_k320_forward failed ({ret}): {L.gd_nn_linear_320_last_error().decode()}")
+    launch("gd_nn_linear_k320_forward", x.device, x, weight, bias, y, M, N)
     return y
 
 
@@ -2280,13 +2045,7 @@ def linear_320_geglu(x, weight, bias=None):
     GEGLU arithmetic in the streaming GEMM's store phase); bit-identical to ``geglu(linear_320(x, weight, bias))``."""
     M, inner = x.numel() // 320, weight.shape[0] // 2
     y = torch.empty(x.shape[:-1] + (inner,), dtype=torch.bfloat16, device=x.device)
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_linear_k320_geglu_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(),
-                                                weight.data_ptr(), None if bias is None else bias.data_ptr(), y.data_ptr(),
-                                                M, inner)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_linear_k320_geglu_forward failed ({ret}): {L.gd_nn_linear_320_last_error().decode()}")
+    launch("gd_nn_linear_k320_geglu_forward", x.device, x, weight, bias, y, M, inner)
     return y
 
 
@@ -2315,13 +2074,7 @@ def gemm(x, weight, bias=None, residual=None):
     K = weight.shape[1]
     M = x.numel() // K
     y = torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=torch.bfloat16, device=x.device)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_gemm_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), weight.data_ptr(), p(bias),
-                                   p(residual), y.data_ptr(), M, K, weight.shape[0])
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_gemm_forward failed ({ret}): {L.gd_nn_gemm_last_error().decode()}")
+    launch("gd_nn_gemm_forward", x.device, x, weight, bias, residual, y, M, K, weight.shape[0])
     return y
 
 
@@ -2331,12 +2084,7 @@ def gemm_geglu(x, weight, bias=None):
     K = weight.shape[1]
     M, inner = x.numel() // K, weight.shape[0] // 2
     y = torch.empty(x.shape[:-1] + (inner,), dtype=torch.bfloat16, device=x.device)
-    L = lib()
-    with torch.cuda.device(x.device):
-        ret = L.gd_nn_gemm_geglu_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), weight.data_ptr(),
-                                         None if bias is None else bias.data_ptr(), y.data_ptr(), M, K, inner)
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_gemm_geglu_forward failed ({ret}): {L.gd_nn_gemm_last_error().decode()}")
+    launch("gd_nn_gemm_geglu_forward", x.device, x, weight, bias, y, M, K, inner)
     return y
 
 
@@ -2345,10 +2093,5 @@ def linear(x, weight, bias=None, residual=None):
     K = weight.shape[1]
     M = x.numel() // K
     y = torch.empty(x.shape[:-1] + (weight.shape[0],), dtype=torch.bfloat16, device=x.device)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    with torch.cuda.device(x.device):
-        ret = lib().gd_nn_linear_forward(torch.cuda.current_stream(x.device).cuda_stream, x.data_ptr(), weight.data_ptr(),
-                                         p(bias), p(residual), y.data_ptr(), M, K, weight.shape[0])
-    if ret < 0:
-        raise RuntimeError(f"gd_nn_linear_forward failed ({ret}): {lib().gd_nn_conv_last_error().decode()}")
+    launch("gd_nn_linear_forward", x.device, x, weight, bias, residual, y, M, K, weight.shape[0])
     return y
