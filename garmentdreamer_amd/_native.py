@@ -276,6 +276,15 @@ TEXTURE_SORTED_SIGNATURES = {
                                                                                     # db2, then denc slab_scratch sort_scratch
 }
 
+# its opt-in gradient to the sample positions (include/gd_texture_position.h); messages go through gd_texture_last_error
+TEXTURE_POSITION_SIGNATURES = {
+    "gd_texture_encode_backward_pos": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout, _vp, _vp]),  # stream, N, x mask grid, layout, denc dx
+    "gd_texture_field_backward_pos": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout] + [_vp] * 13),  # as field_backward up to db2,
+                                                                                                   # then dx scratch
+    "gd_texture_field_backward_sorted_pos": (_i, [_vp, _i, _vp, _vp, _vp, TextureLayout] + [_vp] * 15),  # as ..._sorted up to
+                                                                                         # denc, then dx slab_scratch sort_scratch
+}
+
 # the texture bake's padding: nearest covered texel and the 8-bit gather (include/gd_bake.h)
 BAKE_MAX_PADDING = 64
 BAKE_MAX_CHANNELS = 4
@@ -410,6 +419,7 @@ def lib():
                 + list(MESH_DEFORM_SIGNATURES.items()) + list(MESH_GEOMETRY_SIGNATURES.items()) \
                 + list(MESH_REMESH_SIGNATURES.items()) + list(MESH_SIMPLIFY_SIGNATURES.items()) \
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
+                + list(TEXTURE_POSITION_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()) \
                 + list(ATLAS_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface

@@ -19,6 +19,9 @@
 //                               reproducible form (include/gd_texture_sorted.h) has its entries here and its kernels in
 //                               raster_texture_sorted.hip; its fused variant is field_backward_kernel<true>, which stores
 //                               denc [N][32] instead of scattering it.
+//   dx                          the opt-in gradient to the positions (include/gd_texture_position.h): position_level gathers
+//                               each corner once; alone in encode_backward_pos_kernel, or in field_backward_pos_kernel beside
+//                               the scatter (or the store of denc), the levels in a rolled loop with denc in LDS.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -26,6 +29,7 @@
 
 #include "../../include/gd_texture.h"
 #include "../../include/gd_texture_sorted.h"
+#include "../../include/gd_texture_position.h"
 #include "raster_texture_cells.h"
 
 namespace gd {
@@ -47,6 +51,7 @@ constexpr int kSlabRow = 1156;
 constexpr int kBwdThreads = 128;      // points per pass of a backward workgroup
 constexpr int kRowStride = 36;        // floats per point in the LDS images of enc and h: rows stay 16-byte aligned
 constexpr int kMaxSlabRows = 1024;
+constexpr int kDencStride = 33;       // floats per point in the LDS image of denc (field_backward_pos_kernel): odd, no conflicts
 constexpr int kSumCols = 16, kSumGroups = 16;
 
 __device__ __forceinline__ float2 encode_level(const float2* __restrict__ grid, const Level& lv, const float u[3])
@@ -74,6 +79,39 @@ __device__ __forceinline__ void scatter_level(float* __restrict__ dgrid, const L
         atomicAdd(dst, w * d0);
         atomicAdd(dst + 1, w * d1);
     }
+}
+
+// One level of the gradient to the position (DEFINITION: include/gd_texture_position.h): S_d over the eight corners, each
+// grid entry gathered once; with kScatter the corner's dgrid contribution is added in the same step, the two atomics being
+// those of scatter_level bit for bit.  Returns with dx_d = dx_d + (0.5 s_l) S_d.
+template <bool kScatter>
+__device__ __forceinline__ void position_level(const float2* __restrict__ grid, float* __restrict__ dgrid, const Level& lv,
+                                               const float u[3], float d0, float d1, float dx[3])
+{
+    const Cell ce = cell_of(u, lv.scale);
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const size_t e = (size_t)lv.offset + corner_index(lv, ce, i);
+        const float2 g = grid[e];
+        const float a = (i & 1) ? ce.w[0] : 1.0f - ce.w[0];
+        const float b = (i & 2) ? ce.w[1] : 1.0f - ce.w[1];
+        const float c = (i & 4) ? ce.w[2] : 1.0f - ce.w[2];
+        if constexpr (kScatter) {
+            const float w = (a * b) * c;          // corner_weight
+            atomicAdd(dgrid + e * GD_TEXTURE_FEATURES, w * d0);
+            atomicAdd(dgrid + e * GD_TEXTURE_FEATURES + 1, w * d1);
+        }
+        const float t = d0 * g.x + d1 * g.y;
+        const float q0 = (b * c) * t, q1 = (a * c) * t, q2 = (a * b) * t;
+        s0 = (i & 1) ? s0 + q0 : s0 - q0;
+        s1 = (i & 2) ? s1 + q1 : s1 - q1;
+        s2 = (i & 4) ? s2 + q2 : s2 - q2;
+    }
+    const float k = 0.5f * lv.scale;
+    dx[0] = dx[0] + k * s0;
+    dx[1] = dx[1] + k * s1;
+    dx[2] = dx[2] + k * s2;
 }
 
 // ---- the encoding on its own ---------------------------------------------------------------------------------------------
@@ -108,6 +146,25 @@ __global__ __launch_bounds__(256) void encode_backward_kernel(int N, const float
     for (int l = 0; l < lay.num_levels; l++) {
         scatter_level(dgrid, level_of(lay, l), u, d[2 * l], d[2 * l + 1]);
     }
+}
+
+// dx [N][3], every row written
+__global__ __launch_bounds__(256) void encode_backward_pos_kernel(int N, const float* __restrict__ x,
+                                                                  const uint8_t* __restrict__ mask,
+                                                                  const float2* __restrict__ grid, gd_texture_layout lay,
+                                                                  const float* __restrict__ denc, float* __restrict__ dx)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    float u[3];
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (load_point(n, N, x, mask, u)) {
+        const float* d = denc + (size_t)n * lay.num_levels * GD_TEXTURE_FEATURES;
+        for (int l = 0; l < lay.num_levels; l++)
+            position_level<false>(grid, nullptr, level_of(lay, l), u, d[2 * l], d[2 * l + 1], acc);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) dx[3 * (size_t)n + c] = acc[c];
 }
 
 // ---- the fused field -----------------------------------------------------------------------------------------------------
@@ -181,12 +238,16 @@ __global__ __launch_bounds__(256) void field_forward_kernel(int N, const float* 
 // kStoreDenc = false: denc is scattered into dgrid with atomics.  kStoreDenc = true (the sorted path): dgrid is not touched
 // and the point's row of denc [N][32] is stored instead, zeros for a point that takes no part; the same parameter carries
 // either pointer, so that the atomic instantiation keeps its signature and its code.
-template <bool kStoreDenc>
-__global__ __launch_bounds__(kBwdThreads) void field_backward_kernel(
+//
+// kPosGrad (include/gd_texture_position.h): dx [N][3] is written beside it, every row; the levels then go through
+// position_level, which gathers each corner's grid entry where its contribution is (or, on the sorted path, would be)
+// scattered.  The body is shared; the kernels without dx keep their signatures.
+template <bool kStoreDenc, bool kPosGrad>
+__device__ __forceinline__ void field_backward_body(
     int N, int nchunks, const float* __restrict__ x, const uint8_t* __restrict__ mask, const float2* __restrict__ grid,
-    gd_texture_layout lay, const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
-    const float* __restrict__ b2, const float* __restrict__ color, const float* __restrict__ dcolor,
-    float* __restrict__ dgrid, float* __restrict__ slab)
+    const gd_texture_layout& lay, const float* __restrict__ w1, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ color,
+    const float* __restrict__ dcolor, float* __restrict__ dgrid, float* __restrict__ slab, float* __restrict__ dx)
 {
     __shared__ float mlp[kSlabRow];
     __shared__ __align__(16) float encS[kBwdThreads * kRowStride];
@@ -238,12 +299,33 @@ __global__ __launch_bounds__(kBwdThreads) void field_backward_kernel(
 #pragma unroll
                 for (int k = 0; k < kWidth / 4; k++)
                     row[k] = make_float4(denc[4 * k], denc[4 * k + 1], denc[4 * k + 2], denc[4 * k + 3]);
-            } else {
+            } else if constexpr (!kPosGrad) {
 #pragma unroll
                 for (int l = 0; l < kLevels; l++) scatter_level(dgrid, level_of(lay, l), u, denc[2 * l], denc[2 * l + 1]);
             }
+            if constexpr (kPosGrad) {
+                // the levels in a ROLLED loop, denc read back from the thread's own LDS row: unrolled over the 16 levels the
+                // compiler forms all 128 corner addresses and weights ahead of the gathers and the atomic instantiation
+                // spills (172 bytes a lane on top of 256 + 256 registers)
+                __shared__ float dencS[kBwdThreads * kDencStride];
+#pragma unroll
+                for (int k = 0; k < kWidth; k++) dencS[t * kDencStride + k] = denc[k];
+                float acc[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+                for (int l = 0; l < kLevels; l++)
+                    position_level<!kStoreDenc>(grid, dgrid, level_of(lay, l), u, dencS[t * kDencStride + 2 * l],
+                                                dencS[t * kDencStride + 2 * l + 1], acc);
+#pragma unroll
+                for (int c = 0; c < 3; c++) dx[3 * (size_t)n + c] = acc[c];
+            }
         } else {
             for (int j = 0; j < kWidth; j++) hS[t * kRowStride + j] = 0.0f;
+            if constexpr (kPosGrad) {
+                if (n < N) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) dx[3 * (size_t)n + c] = 0.0f;
+                }
+            }
             if constexpr (kStoreDenc) {
                 if (n < N) {
                     float4* row = reinterpret_cast<float4*>(dgrid + (size_t)n * kWidth);
@@ -288,6 +370,27 @@ __global__ __launch_bounds__(kBwdThreads) void field_backward_kernel(
     if (kw == 0) row[kB1 + jw] = ab1;
     if (t < 3 * kWidth) row[kW2 + t] = aw2;
     if (t < 3) row[kB2 + t] = ab2;
+}
+
+template <bool kStoreDenc>
+__global__ __launch_bounds__(kBwdThreads) void field_backward_kernel(
+    int N, int nchunks, const float* __restrict__ x, const uint8_t* __restrict__ mask, const float2* __restrict__ grid,
+    gd_texture_layout lay, const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+    const float* __restrict__ b2, const float* __restrict__ color, const float* __restrict__ dcolor,
+    float* __restrict__ dgrid, float* __restrict__ slab)
+{
+    field_backward_body<kStoreDenc, false>(N, nchunks, x, mask, grid, lay, w1, b1, w2, b2, color, dcolor, dgrid, slab,
+                                           nullptr);
+}
+
+template <bool kStoreDenc>
+__global__ __launch_bounds__(kBwdThreads) void field_backward_pos_kernel(
+    int N, int nchunks, const float* __restrict__ x, const uint8_t* __restrict__ mask, const float2* __restrict__ grid,
+    gd_texture_layout lay, const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
+    const float* __restrict__ b2, const float* __restrict__ color, const float* __restrict__ dcolor,
+    float* __restrict__ dgrid, float* __restrict__ slab, float* __restrict__ dx)
+{
+    field_backward_body<kStoreDenc, true>(N, nchunks, x, mask, grid, lay, w1, b1, w2, b2, color, dcolor, dgrid, slab, dx);
 }
 
 // dst[e] += sum of the slab's rows, ascending: thread (column, group) adds rows group, group + 16, ... from 0, then the 16
@@ -490,6 +593,67 @@ int gd_texture_field_backward_sorted(void* stream, int N, const float* x, const 
     const int rows = backward_rows(N);
     hipLaunchKernelGGL(field_backward_kernel<true>, dim3((unsigned)rows), dim3(kBwdThreads), 0, s, N, backward_chunks(N),
                        x, mask, (const float2*)grid, layout, w1, b1, w2, b2, color, dcolor, denc, (float*)slab_scratch);
+    hipLaunchKernelGGL(slab_sum_kernel, grid_of(kMlpFloats, kSumCols), dim3(kSumCols * kSumGroups), 0, s, rows,
+                       (const float*)slab_scratch, dw1, db1, dw2, db2);
+    launch_sorted_dgrid(s, N, x, mask, denc, layout, dgrid, sort_scratch);
+    return launched(what);
+}
+
+// ---- the gradient to the positions (include/gd_texture_position.h) --------------------------------------------------------
+
+int gd_texture_encode_backward_pos(void* stream, int N, const float* x, const uint8_t* mask, const float* grid,
+                                   gd_texture_layout layout, const float* denc, float* dx)
+{
+    using namespace gd;
+    if (int r = check_common("encode backward pos", N, layout, !x || !grid || !denc || !dx, grid)) return r;
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(encode_backward_pos_kernel, grid_of(N, 256), dim3(256), 0, (hipStream_t)stream, N, x, mask,
+                       (const float2*)grid, layout, denc, dx);
+    return launched("encode backward pos");
+}
+
+int gd_texture_field_backward_pos(void* stream, int N, const float* x, const uint8_t* mask, const float* grid,
+                                  gd_texture_layout layout, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, const float* color, const float* dcolor, float* dgrid, float* dw1,
+                                  float* db1, float* dw2, float* db2, float* dx, void* scratch)
+{
+    using namespace gd;
+    const char* what = "field backward pos";
+    const bool nulls = !x || !grid || !w1 || !b1 || !w2 || !b2 || !color || !dcolor || !dgrid || !dw1 || !db1 || !dw2 ||
+                       !db2 || !dx || !scratch;
+    if (int r = check_common(what, N, layout, nulls, grid)) return r;
+    if (int r = need_field_width(what, layout)) return r;
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = backward_rows(N);
+    hipLaunchKernelGGL(field_backward_pos_kernel<false>, dim3((unsigned)rows), dim3(kBwdThreads), 0, s, N,
+                       backward_chunks(N), x, mask, (const float2*)grid, layout, w1, b1, w2, b2, color, dcolor, dgrid,
+                       (float*)scratch, dx);
+    hipLaunchKernelGGL(slab_sum_kernel, grid_of(kMlpFloats, kSumCols), dim3(kSumCols * kSumGroups), 0, s, rows,
+                       (const float*)scratch, dw1, db1, dw2, db2);
+    return launched(what);
+}
+
+int gd_texture_field_backward_sorted_pos(void* stream, int N, const float* x, const uint8_t* mask, const float* grid,
+                                         gd_texture_layout layout, const float* w1, const float* b1, const float* w2,
+                                         const float* b2, const float* color, const float* dcolor, float* dgrid,
+                                         float* dw1, float* db1, float* dw2, float* db2, float* denc, float* dx,
+                                         void* slab_scratch, void* sort_scratch)
+{
+    using namespace gd;
+    const char* what = "field backward sorted pos";
+    const bool nulls = !x || !grid || !w1 || !b1 || !w2 || !b2 || !color || !dcolor || !dgrid || !dw1 || !db1 || !dw2 ||
+                       !db2 || !denc || !dx || !slab_scratch || !sort_scratch;
+    if (int r = check_common(what, N, layout, nulls, grid)) return r;
+    if (int r = need_field_width(what, layout)) return r;
+    if (int r = need_sorted_points(what, N)) return r;
+    if ((uintptr_t)denc & 15) return tfail(-1, "field backward sorted pos: denc must be 16-byte aligned");
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = backward_rows(N);
+    hipLaunchKernelGGL(field_backward_pos_kernel<true>, dim3((unsigned)rows), dim3(kBwdThreads), 0, s, N,
+                       backward_chunks(N), x, mask, (const float2*)grid, layout, w1, b1, w2, b2, color, dcolor, denc,
+                       (float*)slab_scratch, dx);
     hipLaunchKernelGGL(slab_sum_kernel, grid_of(kMlpFloats, kSumCols), dim3(kSumCols * kSumGroups), 0, s, rows,
                        (const float*)slab_scratch, dw1, db1, dw2, db2);
     launch_sorted_dgrid(s, N, x, mask, denc, layout, dgrid, sort_scratch);

@@ -16,8 +16,14 @@ netf/render/texture_encoder.py:8-37 (tiny-cuda-nn's "Grid"/"Hash", linear interp
 Gradients follow ``.grad`` semantics at the C level (every kernel ADDS into the buffer it is given).  A parameter that
 ``TextureFieldOptimizer`` has re-seated carries ``_gd_grad_sink`` (a view of the optimizer's flat gradient buffer, as
 ``flat_adam.FlatAdam`` gives the LoRA adapters): the backward adds straight into it and returns nothing to autograd.
-Without a sink the backward allocates a zeroed gradient and returns it.  There is no gradient to ``x``: the live
-configuration has ``fix_geo: true``; ``x.requires_grad`` raises.
+Without a sink the backward allocates a zeroed gradient and returns it.
+
+The gradient to ``x`` is opt-in (``position_gradient=True`` on ``encode``, ``field``, ``HashGridEncoder``, ``TextureField``;
+kernels and definition: include/gd_texture_position.h): the derivative of the trilinear interpolation inside the cell the
+forward chose, written (not added) by the same pass that forms the other gradients, no atomics, bit-reproducible; no double
+backward.  It is what ``netf_geometry.DeformableNeTFRenderer`` (``fix_geo: false``) moves the vertices with.  Without the
+flag, the live configuration's ``fix_geo: true``, nothing changes: ``x.requires_grad`` raises.  With the flag and an ``x`` that
+needs no gradient the launches are the ones without it.
 
 Determinism.  Every forward and the MLP gradients are bit-reproducible.  The gradient to the grid is by default accumulated
 with float atomics (as tiny-cuda-nn does): its last bits differ between runs.  ``deterministic=True`` (``encode``, ``field``,
@@ -35,6 +41,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _native
 from ._launch import launch, require_gpu, scratch
@@ -44,7 +51,7 @@ from .mesh_render import MeshRenderer
 FEATURES = 2
 FIELD_WIDTH = 32
 _X_GRAD = ("gradients with respect to the sample positions are not implemented: detach x, or keep the geometry fixed "
-           "(fix_geo: true)")
+           "(fix_geo: true)")      # without position_gradient=True, that is (include/gd_texture_position.h)
 
 
 class GridLayout(NamedTuple):
@@ -101,12 +108,14 @@ def grid_layout(num_levels: int = 16, base_resolution: int = 16, per_level_scale
     return GridLayout(num_levels, scale, res, size, offset, res ** 3 <= size)
 
 
-def _points(name: str, x, mask):
-    """(x [N,3] contiguous and detached, mask uint8 [N] or None)"""
+def _points(name: str, x, mask, position_gradient: bool = False):
+    """(x [N,3] contiguous, mask uint8 [N] or None); x is detached unless it requires a gradient and ``position_gradient``
+    asks for one: then autograd sees it, and the backward returns ``dx`` to it"""
     require_gpu(name, "x", x, torch.float32)
     if x.dim() != 2 or x.shape[1] != 3:
         raise ValueError(f"{name}: x must be [N,3]")
-    if x.requires_grad and torch.is_grad_enabled():
+    wants_dx = x.requires_grad and torch.is_grad_enabled()
+    if wants_dx and not position_gradient:
         raise NotImplementedError(f"{name}: " + _X_GRAD)
     if mask is not None:
         require_gpu(name, "mask", mask)
@@ -118,7 +127,7 @@ def _points(name: str, x, mask):
         elif mask.dtype != torch.uint8:
             raise TypeError(f"{name}: mask must be bool or uint8")
         mask = mask.contiguous()
-    return x.detach().contiguous(), mask
+    return (x if wants_dx else x.detach()).contiguous(), mask
 
 
 def _sinks(params):
@@ -147,6 +156,8 @@ def _sort_scratch(n: int, struct, dev) -> torch.Tensor:
 
 
 class _Encode(torch.autograd.Function):
+    """``x`` reaches autograd only where ``_points`` let it (``position_gradient``): then the backward returns ``dx``"""
+
     @staticmethod
     def forward(ctx, x, mask, grid, layout, struct, deterministic):
         enc = torch.empty((x.shape[0], layout.output_dim), dtype=torch.float32, device=x.device)
@@ -156,15 +167,20 @@ class _Encode(torch.autograd.Function):
         return enc
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, denc):
         x, mask, grid = ctx.saved_tensors
         (buf, ret), = _grad_targets([grid], ctx.sinks)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            launch("gd_texture_encode_backward_pos", x.device, x.shape[0], x, mask, grid, ctx.struct, denc.contiguous(), dx)
         if ctx.deterministic:
             launch("gd_texture_encode_backward_sorted", x.device, x.shape[0], x, mask, denc.contiguous(), ctx.struct, buf,
                    _sort_scratch(x.shape[0], ctx.struct, x.device))
         else:
             launch("gd_texture_encode_backward", x.device, x.shape[0], x, mask, denc.contiguous(), ctx.struct, buf)
-        return None, None, ret, None, None, None
+        return dx, None, ret, None, None, None
 
 
 class _Field(torch.autograd.Function):
@@ -177,6 +193,7 @@ class _Field(torch.autograd.Function):
         return color
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dcolor):
         x, mask, grid, w1, b1, w2, b2, color = ctx.saved_tensors
         dev = x.device
@@ -184,14 +201,16 @@ class _Field(torch.autograd.Function):
         dcolor = dcolor.contiguous()
         targets = _grad_targets([grid, w1, b1, w2, b2], ctx.sinks)
         slab = scratch(_native.lib().gd_texture_field_backward_scratch_bytes(n), dev)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None        # the same pass writes it (..._pos entries)
+        pos, extra = ("_pos", [dx]) if dx is not None else ("", [])
         if ctx.deterministic:
             denc = torch.empty((n, FIELD_WIDTH), dtype=torch.float32, device=dev)
-            launch("gd_texture_field_backward_sorted", dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
-                   *[t[0] for t in targets], denc, slab, _sort_scratch(n, ctx.struct, dev))
+            launch("gd_texture_field_backward_sorted" + pos, dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color,
+                   dcolor, *[t[0] for t in targets], denc, *extra, slab, _sort_scratch(n, ctx.struct, dev))
         else:
-            launch("gd_texture_field_backward", dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
-                   *[t[0] for t in targets], slab)
-        return (None, None) + tuple(t[1] for t in targets) + (None, None)
+            launch("gd_texture_field_backward" + pos, dev, n, x, mask, grid, ctx.struct, w1, b1, w2, b2, color, dcolor,
+                   *[t[0] for t in targets], *extra, slab)
+        return (dx, None) + tuple(t[1] for t in targets) + (None, None)
 
 
 def _param(name: str, what: str, p: torch.Tensor, shape) -> torch.Tensor:
@@ -202,19 +221,22 @@ def _param(name: str, what: str, p: torch.Tensor, shape) -> torch.Tensor:
 
 
 def encode(x: torch.Tensor, grid: torch.Tensor, layout: GridLayout, mask: Optional[torch.Tensor] = None,
-           deterministic: bool = False) -> torch.Tensor:
+           deterministic: bool = False, position_gradient: bool = False) -> torch.Tensor:
     """``enc`` float32 [N, L F] of the points ``x`` [N,3] (in [-1, 1]^3; anything finite is defined) in the flat table
     ``grid``; rows with ``mask == 0`` or a non-finite coordinate are 0 and pass no gradient.  ``deterministic``: the
-    gradient to ``grid`` by sort and sum instead of atomics (see the module's docstring)."""
+    gradient to ``grid`` by sort and sum instead of atomics (see the module's docstring).  ``position_gradient``: an ``x``
+    that requires a gradient gets one (include/gd_texture_position.h) instead of raising."""
     _param("encode", "grid", grid, (layout.num_params,))
-    x, mask = _points("encode", x, mask)
+    x, mask = _points("encode", x, mask, bool(position_gradient))
     return _Encode.apply(x, mask, grid, layout, layout.struct(), bool(deterministic))
 
 
 def field(x: torch.Tensor, grid: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
-          layout: GridLayout, mask: Optional[torch.Tensor] = None, deterministic: bool = False) -> torch.Tensor:
+          layout: GridLayout, mask: Optional[torch.Tensor] = None, deterministic: bool = False,
+          position_gradient: bool = False) -> torch.Tensor:
     """``color`` float32 [N,3] = sigmoid(W2 relu(W1 enc + b1) + b2), one launch; needs ``L F = 32``.  ``deterministic``:
-    the gradient to ``grid`` by sort and sum instead of atomics (see the module's docstring)."""
+    the gradient to ``grid`` by sort and sum instead of atomics (see the module's docstring).  ``position_gradient``: an
+    ``x`` that requires a gradient gets one, from the same backward pass, instead of raising."""
     if layout.output_dim != FIELD_WIDTH:
         raise ValueError(f"field: the fused path needs num_levels * level_dim = {FIELD_WIDTH}")
     _param("field", "grid", grid, (layout.num_params,))
@@ -222,18 +244,19 @@ def field(x: torch.Tensor, grid: torch.Tensor, w1: torch.Tensor, b1: torch.Tenso
     _param("field", "b1", b1, (FIELD_WIDTH,))
     _param("field", "w2", w2, (3, FIELD_WIDTH))
     _param("field", "b2", b2, (3,))
-    x, mask = _points("field", x, mask)
+    x, mask = _points("field", x, mask, bool(position_gradient))
     return _Field.apply(x, mask, grid, w1, b1, w2, b2, layout.struct(), bool(deterministic))
 
 
 class HashGridEncoder(nn.Module):
     """The reference's ``HashGridEncoder`` (texture_encoder.py:8-37): same signature, same ``per_level_scale``; ``params`` is
     the flat table in tiny-cuda-nn's order (level, entry, feature), uniform in [-1e-4, 1e-4].  ``deterministic`` (kept as
-    ``.deterministic``): the gradient to ``params`` by sort and sum instead of atomics."""
+    ``.deterministic``): the gradient to ``params`` by sort and sum instead of atomics.  ``position_gradient`` (kept as
+    ``.position_gradient``): ``x`` may require a gradient and gets one."""
 
     def __init__(self, input_dim=3, num_levels=16, level_dim=2, log2_hashmap_size=19, base_resolution=16,
                  desired_resolution=1024, interpolation="linear", generator: Optional[torch.Generator] = None,
-                 deterministic: bool = False):
+                 deterministic: bool = False, position_gradient: bool = False):
         super().__init__()
         if input_dim != 3 or level_dim != FEATURES:
             raise NotImplementedError("HashGridEncoder: only input_dim=3 and level_dim=2 are built")
@@ -241,28 +264,29 @@ class HashGridEncoder(nn.Module):
             raise NotImplementedError("HashGridEncoder: only linear interpolation is built (the reference never asks "
                                       "for smoothstep)")
         self._set_layout(grid_layout(num_levels, base_resolution, None, log2_hashmap_size, desired_resolution), generator,
-                         deterministic)
+                         deterministic, position_gradient)
 
-    def _set_layout(self, layout: GridLayout, generator, deterministic=False):
+    def _set_layout(self, layout: GridLayout, generator, deterministic=False, position_gradient=False):
         self.layout = layout
         self.deterministic = bool(deterministic)
+        self.position_gradient = bool(position_gradient)
         self.input_dim = 3
         self.output_dim = layout.output_dim
         self.params = nn.Parameter((torch.rand(layout.num_params, generator=generator) * 2 - 1) * 1e-4)
 
     @classmethod
     def from_layout(cls, layout: GridLayout, generator: Optional[torch.Generator] = None,
-                    deterministic: bool = False) -> "HashGridEncoder":
+                    deterministic: bool = False, position_gradient: bool = False) -> "HashGridEncoder":
         """An encoder over any ``grid_layout(...)`` (the constructor's arguments cannot state ``per_level_scale``)."""
         self = cls.__new__(cls)
         nn.Module.__init__(self)
-        self._set_layout(layout, generator, deterministic)
+        self._set_layout(layout, generator, deterministic, position_gradient)
         return self
 
     def forward(self, x, bound=1, mask=None):
         if bound != 1:
             raise ValueError("HashGridEncoder: only bound=1 is built")
-        return encode(x, self.params, self.layout, mask, self.deterministic)
+        return encode(x, self.params, self.layout, mask, self.deterministic, self.position_gradient)
 
 
 WEIGHT_GRAD_BLOCK = 128
@@ -319,14 +343,17 @@ class TextureField(nn.Module):
     """``sigmoid(mlp(encoder(x)))`` in one launch forward, and one launch plus the fixed-order sum backward.
     ``encoder``: a ``HashGridEncoder`` with ``output_dim == 32`` (default: the reference's).  ``generator`` seeds the grid;
     the MLP is ``nn.Linear``-initialised from torch's global generator.  ``deterministic``: if not ``None`` it is set on
-    the encoder; ``forward``, ``unfused`` and ``.encoder(...)`` all follow ``encoder.deterministic``."""
+    the encoder; ``forward``, ``unfused`` and ``.encoder(...)`` all follow ``encoder.deterministic``.
+    ``position_gradient``: the same pattern, ``encoder.position_gradient``."""
 
     def __init__(self, encoder: Optional[HashGridEncoder] = None, generator: Optional[torch.Generator] = None,
-                 deterministic: Optional[bool] = None):
+                 deterministic: Optional[bool] = None, position_gradient: Optional[bool] = None):
         super().__init__()
         self.encoder = encoder if encoder is not None else HashGridEncoder(generator=generator)
         if deterministic is not None:
             self.encoder.deterministic = bool(deterministic)
+        if position_gradient is not None:
+            self.encoder.position_gradient = bool(position_gradient)
         if self.encoder.output_dim != FIELD_WIDTH:
             raise ValueError(f"TextureField: the fused path needs an encoder with output_dim = {FIELD_WIDTH}")
         self.mlp = AlbedoMLP()
@@ -334,7 +361,7 @@ class TextureField(nn.Module):
     def forward(self, x, mask=None):
         l1, l2 = self.mlp.net
         return field(x, self.encoder.params, l1.weight, l1.bias, l2.weight, l2.bias, self.encoder.layout, mask,
-                     self.encoder.deterministic)
+                     self.encoder.deterministic, self.encoder.position_gradient)
 
     def unfused(self, x, mask=None):
         """The same function through ``.encoder`` and ``.mlp`` (the [N,32] encoding goes through memory)."""
