@@ -42,6 +42,7 @@ RASTER_SOURCES = [
     ("raster_atlas.hip", ["-ffp-contract=off"]),      # include/gd_atlas.h fixes the order (tests/atlas_reference.py)
     ("raster_sample.hip", ["-ffp-contract=off"]),     # include/gd_sample.h likewise (tests/sample_reference.py)
     ("raster_clean.hip", ["-ffp-contract=off"]),      # include/gd_mesh_clean.h likewise (tests/clean_reference.py)
+    ("raster_views.hip", ["-ffp-contract=off"]),      # include/gd_views.h likewise (tests/views_reference.py)
     ("raster_shader.hip", ["-ffp-contract=off"]),     # the fp32 side of include/gd_shader.h: every operation in its order
     ("raster_shader_mfma.hip", []),                   # its eight products on the bf16 matrix cores
 ]

@@ -234,6 +234,16 @@ MESH_CLEAN_SIGNATURES = {
                                            # used vscan target parent crank sorted_keys verts_out tri_out face_map vertex_map
 }
 
+# reading the captured views: the PNG row unfilter and the unpacking into float images (include/gd_views.h); messages go
+# through gd_mesh_last_error
+VIEWS_MAX_SIDE = 8192
+VIEWS_SIGNATURES = {
+    "gd_views_png_unfilter": (_i, [_vp, _vp, _vp] + [_i] * 4),                     # stream, filtered out, B H W bpp
+    "gd_views_unpack": (_i, [_vp, _vp, _vp, _i] + [_vp] * 3 + [_i] * 2),           # stream, normal_rgba rgb, rgb_channels,
+                                                                                   # normal mask rgb_out, H W
+    "gd_views_unpack_rgba": (_i, [_vp] * 4 + [_i] * 2),                            # stream, rgba rgb_out mask, H W
+}
+
 # the second stage's G-buffer losses: enhanced / plain normal map and hole mask, one view per call (include/gd_mesh_losses.h)
 MESH_LOSS_ENHANCED, MESH_LOSS_PLAIN, MESH_LOSS_HOLE = 1, 2, 4
 MESH_LOSS_STATS_WORDS = 6
@@ -421,7 +431,8 @@ def lib():
                 + list(MESH_LOSS_SIGNATURES.items()) + list(TEXTURE_SIGNATURES.items()) + list(TEXTURE_SORTED_SIGNATURES.items()) \
                 + list(TEXTURE_POSITION_SIGNATURES.items()) \
                 + list(BAKE_SIGNATURES.items()) + list(SHADER_SIGNATURES.items()) + list(FIT_SIGNATURES.items()) \
-                + list(ATLAS_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()):
+                + list(ATLAS_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(MESH_CLEAN_SIGNATURES.items()) \
+                + list(VIEWS_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError here == ABI drift; let it surface
             fn.restype = res
             fn.argtypes = args
@@ -435,6 +446,7 @@ _ERROR_CHANNELS = (("gd_scene_densify_stats", "gd_scene_last_error"), ("gd_scene
                    ("gd_scene_", "gd_scene_last_error"), ("gd_mesh_", "gd_mesh_last_error"),
                    ("gd_shader_", "gd_mesh_last_error"), ("gd_fit_", "gd_mesh_last_error"),
                    ("gd_atlas_", "gd_mesh_last_error"), ("gd_sample_", "gd_mesh_last_error"),
+                   ("gd_views_", "gd_mesh_last_error"),
                    ("gd_texture_", "gd_texture_last_error"), ("gd_bake_", "gd_bake_last_error"),
                    ("gd_raster_", "gd_raster_last_error"))
 

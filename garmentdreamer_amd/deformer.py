@@ -12,21 +12,30 @@ the current mesh on the kernels of ``mesh_remesh`` and ``adopt_remesh`` carries 
 stage's product: the current mesh rotated upright, decimated and smoothed on the kernels of ``mesh_simplify``.  No CPU path
 anywhere.
 
-Out of scope here: reading the views, the space normalisation and the image dumps.
+From disk: ``Deformer.from_views`` / ``begin_second_stage_from_views`` take the views of ``views.read_views``, and
+``run_deformation`` is the whole schedule of ``deformation.py`` on a capture directory: read, adjust, normalise, both stages
+with the upsample, denormalise, post-process, write.
+
+Out of scope here: the image dumps and the parsing of the YAML configuration.
 """
 from __future__ import annotations
 
+import os
 from typing import Callable, Dict, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import mesh_geometry as mg
 from . import mesh_losses as ml
 from . import mesh_remesh as mr
 from . import mesh_simplify as ms
+from . import template
+from . import views as gv
 from ._launch import require_gpu
 from .flat_adam import FlatAdam
 from .mesh_deform import GBufferRenderer
+from .neural_shader import NeuralShader
 
 FIRST_STAGE_WEIGHTS = {"mask": 2, "normal_consistency": 0.1, "laplacian": 800}   # deformation.py, loss_weights_first
 # deformation.py, loss_weights_second with the defaults of its arguments; its "shading": 1.0 is begin_second_stage's
@@ -58,6 +67,13 @@ class Deformer:
         self.offsets = torch.nn.Parameter(torch.zeros_like(self.initial))
         self.optimizer = FlatAdam([self.offsets], lr=lr)
         self.eps = self.optimizer.eps
+
+    @classmethod
+    def from_views(cls, vertices: torch.Tensor, indices: torch.Tensor, views, near: float, far: float, **kw) -> "Deformer":
+        """The constructor fed from ``views.read_views``: one ``to_gl_camera`` matrix per view between ``near`` and ``far``
+        (``views.near_far``), its mask as the target and its resolution; ``kw`` goes to the constructor."""
+        return cls(vertices, indices, gv.view_mvps(views, near, far), [v.mask for v in views],
+                   [v.resolution for v in views], **kw)
 
     @property
     def lr(self) -> float:
@@ -145,6 +161,13 @@ class Deformer:
             self.rf_vertices = (self.initial + self.offsets).detach().clone()
             self.rf_normals = mg.normals(self.rf_vertices, self.rf_geometry)[1]
 
+    def begin_second_stage_from_views(self, views, **kw) -> None:
+        """``begin_second_stage`` with the normal maps, rotations, centres and colour images of ``views`` (the list this
+        object was made from by ``from_views``); ``kw`` carries its other arguments."""
+        dev = self.initial.device
+        self.begin_second_stage([v.normal for v in views], [v.R.to(dev) for v in views], [v.center.to(dev) for v in views],
+                                target_rgbs=[v.rgb for v in views], **kw)
+
     def step_second(self, view_indices: Sequence[int],
                     extra_loss: Optional[Callable[[Sequence[int], Sequence[dict]], torch.Tensor]] = None
                     ) -> Dict[str, torch.Tensor]:
@@ -229,3 +252,90 @@ class Deformer:
                 self.second_weights[k] *= 4
         self.offsets = torch.nn.Parameter(torch.zeros_like(self.initial))
         self.optimizer = FlatAdam([self.offsets], lr=self.lr * 0.25)
+
+
+# ---- the whole stage --------------------------------------------------------------------------------------------------
+
+# configs/garment_deformer_configs.yml of the reference, the keys this schedule reads; ``final_faces`` is the target of
+# write_mesh(..., post_process=True)
+DEFAULT_CONFIG = {
+    "enhanced_normal_map_loss": True, "iterations_first": 3000, "iterations_second": 1000, "upsample_iterations": [3500],
+    "lr_vertices": 0.001, "weight_hole_mask": 2.0, "weight_mask": 2.0, "weight_normal_consistency": 0.1,
+    "weight_laplacian": 40.0, "weight_normal": 0.8, "weight_shading": 1.0, "lr_shader": 0.001, "shading_percentage": 0.75,
+    "hidden_features_layers": 3, "hidden_features_size": 256, "fourier_features": "positional", "activation": "relu",
+    "fft_scale": 4, "picked_views_first": [74, 333],
+    "picked_views_second": [111, 115, 120, 125, 129, 133, 138, 143, 221, 189, 194, 199, 203, 207, 212, 217,
+                            259, 263, 268, 273, 277, 281, 286, 291],
+    "final_faces": 40000,
+}
+
+
+def run_deformation(directory: str, template_obj: str, bound: float, config: Optional[dict] = None) -> Dict[str, str]:
+    """The schedule of ``deformation.py`` on the capture in ``directory`` (``views.read_views``'s layout) from the template
+    mesh ``template_obj``, without the image dumps: the seeds; the template adjusted by ``bound``, its box saved, views,
+    mesh and box normalised, near and far over ALL cameras; the first stage over the views at positions
+    ``picked_views_first[0] .. [1]``, one drawn per iteration; the second stage over ``picked_views_second`` under the
+    visible-rows rule, with ``remesh`` at an upsample iteration; the mesh denormalised, written, post-processed and written
+    again.  ``config``: overrides of ``DEFAULT_CONFIG`` (a dict; YAML is the caller's).  Only the views either stage can
+    draw are read.  Returns the paths written: ``bbox``, ``mesh`` and ``final_mesh``."""
+    unknown = set(config or {}) - set(DEFAULT_CONFIG)
+    if unknown:
+        raise ValueError(f"run_deformation: unknown config keys {sorted(unknown)}")
+    cfg = {**DEFAULT_CONFIG, **(config or {})}
+    np.random.seed(12)
+    torch.manual_seed(123)
+    torch.cuda.manual_seed(123)
+    directory = os.fspath(directory)
+    out_dir = os.path.join(directory, "deformation_check")
+    os.makedirs(os.path.join(out_dir, "meshes"), exist_ok=True)
+
+    cameras = gv.read_cameras(directory)
+    first = [i for i in range(*cfg["picked_views_first"]) if i < len(cameras)]
+    second = sorted(set(int(i) for i in cfg["picked_views_second"] if 0 <= int(i) < len(cameras)))
+    wanted = sorted(set(first) | set(second))
+    views = gv.read_views(directory, indices=wanted)
+    place = {p: k for k, p in enumerate(wanted)}                       # position in the capture -> position in `views`
+
+    v, f = template.load_obj(template_obj)
+    vertices = gv.adjust_template(v, bound).astype(np.float32)
+    aabb = gv.AABB(vertices)
+    paths = {"bbox": os.path.join(out_dir, "bbox.txt")}
+    aabb.save(paths["bbox"])
+    space = gv.SpaceNormalization(aabb.corners)
+    space.normalize_views(views)
+    space.normalize_views(cameras)
+    vertices = space.normalize_mesh(vertices).astype(np.float32)
+    near, far = gv.near_far(cameras, space.normalize_aabb(aabb).corners, epsilon=0.5)
+
+    dev = views[0].mask.device
+    deformer = Deformer.from_views(torch.from_numpy(vertices).to(dev), torch.from_numpy(f.astype(np.int32)).to(dev), views,
+                                   near, far, lr=cfg["lr_vertices"])
+    sampler_first = gv.ViewSampler(views, "several", 1, [place[i] for i in first])
+    sampler_second = gv.ViewSampler(views, "several", 1, [place[i] for i in second])
+    for _ in range(int(cfg["iterations_first"])):
+        deformer.step(sampler_first())
+
+    shader = None
+    if cfg["weight_shading"] > 0:
+        shader = NeuralShader(hidden_features_size=cfg["hidden_features_size"],
+                              hidden_features_layers=cfg["hidden_features_layers"], activation=cfg["activation"],
+                              fourier_features=cfg["fourier_features"], fft_scale=cfg["fft_scale"], device=dev)
+    weights = {"hole_mask": cfg["weight_hole_mask"], "mask": cfg["weight_mask"],
+               "normal_consistency": cfg["weight_normal_consistency"], "laplacian": cfg["weight_laplacian"],
+               "normal": cfg["weight_normal"]}
+    deformer.begin_second_stage_from_views(views, weights=weights, enhanced=bool(cfg["enhanced_normal_map_loss"]),
+                                           shader=shader, shading_percentage=cfg["shading_percentage"],
+                                           shading_weight=cfg["weight_shading"], lr_shader=cfg["lr_shader"])
+    start, total = int(cfg["iterations_first"]) + 1, int(cfg["iterations_first"]) + int(cfg["iterations_second"])
+    for iteration in range(start, total + 1):
+        if iteration in cfg["upsample_iterations"]:
+            deformer.remesh()
+        deformer.step_second(sampler_second())
+
+    final = space.denormalize_mesh((deformer.initial + deformer.offsets).detach())
+    paths["mesh"] = os.path.join(out_dir, "meshes", f"mesh_{total:06d}.obj")
+    ms.write_obj(paths["mesh"], final, deformer.geometry.tri)
+    processed, processed_tri, _ = ms.post_process_mesh(final.contiguous(), deformer.geometry.tri, int(cfg["final_faces"]))
+    paths["final_mesh"] = os.path.join(directory, "final_mesh.obj")
+    ms.write_obj(paths["final_mesh"], processed, processed_tri)
+    return paths

@@ -89,10 +89,11 @@ def save_image_rgb(path: str, rgb8) -> str:
     return path
 
 
-def load_image_rgb(path: str) -> np.ndarray:
-    """uint8 [H,W,3] or [H,W,4] of an 8-bit PNG of colour type 2 (RGB) or 6 (RGBA), not interlaced, row filters 0-4: what
-    ``save_image_rgb`` / ``save_image_rgba`` write and what other writers make of the same pixels.  Anything else (another
-    bit depth or colour type, interlacing, a broken file) raises ``ValueError`` naming it.  ``zlib`` and ``struct`` only."""
+def read_png_stream(path: str):
+    """``(W, H, bpp, rows)`` of the PNG ``load_image_rgb`` reads: the chunks parsed and their CRCs checked, the header
+    checked, the IDAT data inflated (``zlib`` releases the GIL) and its length checked.  ``rows``: the ``H (1 + W bpp)``
+    bytes of the filtered rows, each with its filter type first; the types themselves are the caller's to check.  The one
+    parser of ``load_image_rgb`` and of ``views.decode_png_batch``."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:8] != b"\x89PNG\r\n\x1a\n":
@@ -128,6 +129,19 @@ def load_image_rgb(path: str) -> np.ndarray:
     raw = zlib.decompress(b"".join(idat))
     if len(raw) != H * (stride + 1):
         raise ValueError(f"{path}: {len(raw)} bytes of pixel data, expected {H * (stride + 1)}")
+    return W, H, bpp, raw
+
+
+def undefined_row_filter(path: str, kind: int) -> ValueError:
+    return ValueError(f"{path}: row filter type {kind} is not defined")
+
+
+def load_image_rgb(path: str) -> np.ndarray:
+    """uint8 [H,W,3] or [H,W,4] of an 8-bit PNG of colour type 2 (RGB) or 6 (RGBA), not interlaced, row filters 0-4: what
+    ``save_image_rgb`` / ``save_image_rgba`` write and what other writers make of the same pixels.  Anything else (another
+    bit depth or colour type, interlacing, a broken file) raises ``ValueError`` naming it.  ``zlib`` and ``struct`` only."""
+    W, H, bpp, raw = read_png_stream(path)
+    stride = W * bpp
     rows = np.frombuffer(raw, dtype=np.uint8).reshape(H, stride + 1)
     out = np.zeros((H, stride), dtype=np.uint8)
     prior = np.zeros(stride, dtype=np.int64)
@@ -156,7 +170,7 @@ def load_image_rgb(path: str) -> np.ndarray:
                 res[i] = (src[i] + pred) & 255
             cur[:] = res
         else:
-            raise ValueError(f"{path}: row filter type {kind} is not defined")
+            raise undefined_row_filter(path, kind)
         out[r] = cur
         prior = cur
     return out.reshape(H, W, bpp)
